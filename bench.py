@@ -17,7 +17,14 @@ Both directions are also reported separately from HIP-event kernel times, each w
 algorithmic bytes per launch = sum over blocks of (U_b + C_b)    /  average launch duration, against
 the 8 TB/s HBM3E peak.
 
-When N > 1 (or with --config5-lines) the SAME run then measures BASELINE.json configs[4] -- the mixed-corpus blocks,
+A plain run does only what that line needs: set up, warm up, time --steps steps, check the last step's round trip, write its outputs
+(--dump-outputs DIR) and print the line (its roofline quotes the committed traffic profile).  Everything below -- configs[4] lines,
+cpu_baseline, live roofline traffic, decode alone + clocks, the plain-workspace and default-search values, per_rank, other_configs --
+runs only with --full; the --no-* options and --config5-lines then narrow or widen what --full measures.
+
+--dump-outputs DIR (rank 0): what the last timed step returned, as DIR/<name>.npy in float32 (see dump_outputs).
+
+When N > 1 (or with --config5-lines), with --full, the SAME run then measures BASELINE.json configs[4] -- the mixed-corpus blocks,
 block-sharded across the ranks -- and reports it as `config5_lines` (codec only / + directory gather / + compaction
 and payload gather to rank 0): one driver command covers the 8-GPU workload the north star names.  Never `value`.
 
@@ -316,7 +323,7 @@ def live_traffic(nb: int, hash_name: str, config: int):
     for counter, key in (("FETCH_SIZE", "fetch_bytes"), ("WRITE_SIZE", "write_bytes")):
         d = tempfile.mkdtemp(prefix="snp_pmc_")
         cmd = [tool, "--pmc", counter, "-d", d, "-o", "pmc", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-live-traffic", "--blocks", str(nb), "--hash", hash_name, "--config", str(config)]
+               "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-live-traffic", "--blocks", str(nb), "--hash", hash_name, "--config", str(config)]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
         env.update(BENCH_NO_PLAIN="1", TMPDIR="/tmp")
         try:
@@ -347,6 +354,43 @@ def traffic_profile():
     return {}, None
 
 
+DUMP_SAMPLE_BLOCKS = 48            # blocks whose bytes are written (compressed and decompressed)
+DUMP_MAX_VECTOR_BLOCKS = 1 << 20   # per-block lengths and statuses are written for every block up to this many
+DUMP_SEED = 0x5EED0D0
+
+
+def dump_outputs(directory: str, comp, comp_stride: int, out_len, status, back, dlen, dst) -> dict:
+    """Writes what one step of the timed path returned as DIR/<name>.npy, float32 (every value is an integer below 2**24: exact):
+    compressed_lengths, compress_status, decompressed_lengths, decompress_status -- one entry per block (a fixed, seeded sample of
+    DUMP_MAX_VECTOR_BLOCKS blocks beyond that many) -- and compressed_bytes_sample [k, comp_stride] (bytes past the block's compressed
+    length are written as 0), decompressed_bytes_sample [k, BLOCK] for a fixed, seeded sample of k = min(DUMP_SAMPLE_BLOCKS, blocks)
+    blocks in block order.  The sample depends on the number of blocks only.  At most 64 MB in all.  Returns {name: shape}."""
+    nb = int(out_len.numel())
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.sort(rng.choice(nb, size=min(DUMP_SAMPLE_BLOCKS, nb), replace=False))
+    vidx = np.arange(nb) if nb <= DUMP_MAX_VECTOR_BLOCKS else np.sort(rng.choice(nb, size=DUMP_MAX_VECTOR_BLOCKS, replace=False))
+    t_idx = torch.from_numpy(idx).to(comp.device)
+    t_vidx = torch.from_numpy(vidx).to(out_len.device)
+    lens = out_len.to(torch.int64).cpu().numpy()[idx].clip(0, comp_stride)
+    cbytes = comp[: nb * comp_stride].view(nb, comp_stride).index_select(0, t_idx).cpu().numpy()
+    cbytes[np.arange(comp_stride)[None, :] >= lens[:, None]] = 0
+    arrays = {
+        "compressed_lengths": out_len.index_select(0, t_vidx).cpu().numpy(),
+        "compress_status": status.index_select(0, t_vidx).cpu().numpy(),
+        "compressed_bytes_sample": cbytes,
+        "decompressed_lengths": dlen.index_select(0, t_vidx).cpu().numpy(),
+        "decompress_status": dst.index_select(0, t_vidx).cpu().numpy(),
+        "decompressed_bytes_sample": back[: nb * BLOCK].view(nb, BLOCK).index_select(0, t_idx.to(back.device)).cpu().numpy(),
+    }
+    arrays = {k: v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= 64 * 10**6, f"outputs to dump: {total} bytes"
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -361,13 +405,20 @@ def main():
                     help="the MEASURED workload (`value`): 2 = BASELINE configs[1] (html-like blocks, the headline); 5 = configs[4] (mixed corpus)")
     ap.add_argument("--config5-lines", action="store_true",
                     help="after the measured workload, also run configs[4] (mixed corpus, block-sharded) and report config5_lines; "
-                         "on by default when --gpus > 1")
+                         "with --full only; on by default with --full when --gpus > 1")
     ap.add_argument("--thorough-search", action="store_true",
                     help="build the hash-table workspace with the thorough placement search (SNP_OPT_TABLE_PROBE_TRIES = 24, up to 3/4 of device memory, seconds) "
                          "instead of the library's bounded default; `value` then says so in config.workspace")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip `other_configs` (N = 1 only: BASELINE configs[2], configs[3] and the configs[4] share, 3 steps each, and the CRC kernel; ~15 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what the line reports beside it: configs[4] lines, cpu_baseline, live roofline traffic, decode "
+                         "alone + clocks, value_plain_workspace, value_default_search, per_rank, other_configs (a plain run does none of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32; rank 0's blocks; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -493,17 +544,20 @@ def main():
     # ---- verification (outside the timed region): every status OK, decode(encode(x)) == x -----------------------
     if not verified(out_len, status, dlen, dst):
         sys.exit("[bench] round trip is NOT bit-exact -- number invalid")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, comp, cd.comp_stride, out_len, status, back, dlen, dst)
     c_bytes = float(out_len.to(torch.int64).sum().item())
     u_bytes = float(nb) * BLOCK
     ms_c = float(np.mean([a.elapsed_time(b) for a, b in t_comp]))
     ms_d = float(np.mean([a.elapsed_time(b) for a, b in t_dec]))
-    cpu_sample = raw[: min(args.cpu_sample_blocks, nb) * BLOCK].cpu().numpy() if (world == 1 and rank == 0 and not args.no_cpu_baseline) else None
+    cpu_sample = (raw[: min(args.cpu_sample_blocks, nb) * BLOCK].cpu().numpy()
+                  if (args.full and world == 1 and rank == 0 and not args.no_cpu_baseline) else None)
 
     # ---- the decoder ALONE and the shader clock around the launches: inside the step the decode launch follows a ~96 ms compress
     # launch that is bound by memory latency, and runs 5-9 % slower than in a loop of its own.  Decode-only launches back to back (events), and
     # the clock sampled from sysfs while each kind of launch runs and right after it (host-side sampling of a free-running clock: indicative).
     alone = None
-    if world == 1:
+    if args.full and world == 1:
         rd = sclk_reader(local_rank)
         def sample_during(fn, wait_s):
             """launch fn (asynchronous), read the clock wait_s later (the launch is still running), then right after it has finished"""
@@ -550,7 +604,7 @@ def main():
               "seconds": round(S.lib().snp_ctx_counter(cd.ctx.handle, 4) / 1e6, 3), "chosen_set_probe_ms": S.lib().snp_ctx_counter(cd.ctx.handle, 2) / 1e3,
               "where": "snp_ctx_reserve_compress before the buffers exist (untimed start-up work)" if not os.environ.get("BENCH_NO_RESERVE") else "first compress call (untimed setup pass)"}
     plain = None
-    if lanes and not os.environ.get("BENCH_NO_PLAIN"):
+    if args.full and lanes and not os.environ.get("BENCH_NO_PLAIN"):
         from snappier_amd import _native as N
         cd2 = SB.BlockCodec(local_rank, variant)
         cd2.ctx.set_option(N.OPT_TABLE_PROBE_TRIES, 1)
@@ -582,7 +636,7 @@ def main():
         del cd2
     # ---- what the library's DEFAULT options give: a fresh pool (every context of this process is gone), no option set, no reserve call -------
     default_search = None
-    if lanes and world == 1 and thorough and not os.environ.get("BENCH_NO_DEFAULT_SEARCH"):
+    if args.full and lanes and world == 1 and thorough and not os.environ.get("BENCH_NO_DEFAULT_SEARCH"):
         import gc
         from snappier_amd import batch as SB2
         comp_stride = cd.comp_stride
@@ -620,21 +674,23 @@ def main():
                           "workspace": "library defaults: no option set, no snp_ctx_reserve_compress; the pool is built by the first compress call with this process's buffers already allocated"}
     # ---- per-rank decomposition (N >= 1): which rank was slow, and in which part; the directory gather alone ----
     t_gd = 0.0
-    if distributed:
-        barrier()
-        g0 = time.perf_counter()
-        for _ in range(3):
-            sharding.gather_directory(out_len, status, nb * world)
-        torch.cuda.synchronize()
-        t_gd = (time.perf_counter() - g0) / 3 * 1e3
-    per_rank = sharding.rank_stats({"compress_ms": ms_c, "decompress_ms": ms_d, "workspace_search_s": search["seconds"],
-                                    "directory_gather_ms": t_gd, "plain_compress_ms": plain["compress_ms"] if plain else 0.0}, device=dev)
+    per_rank = None
+    if args.full:
+        if distributed:
+            barrier()
+            g0 = time.perf_counter()
+            for _ in range(3):
+                sharding.gather_directory(out_len, status, nb * world)
+            torch.cuda.synchronize()
+            t_gd = (time.perf_counter() - g0) / 3 * 1e3
+        per_rank = sharding.rank_stats({"compress_ms": ms_c, "decompress_ms": ms_d, "workspace_search_s": search["seconds"],
+                                        "directory_gather_ms": t_gd, "plain_compress_ms": plain["compress_ms"] if plain else 0.0}, device=dev)
     if distributed:
         assert dist.get_world_size() == args.gpus, "rccl_ranks != n_gpus"
 
     # ---- configs[4]: the mixed corpus, block-sharded, and the lines around the codec (never part of `value`) ----------
     extra = {}
-    if args.config == 5 or args.config5_lines or world > 1:
+    if args.full and (args.config == 5 or args.config5_lines or world > 1):
         if args.config != 5:
             del raw
             raw = make_blocks(5)                                # same buffers otherwise: comp, back are reused
@@ -681,7 +737,7 @@ def main():
     # ---- other_configs (N = 1): BASELINE configs[2] (low entropy), configs[3] (framing) and the configs[4] share (mixed corpus) on the same buffers,
     # 3 steps each, verified; and the CRC kernel alone.  Never part of `value`.
     other = None
-    if world == 1 and not args.no_other_configs and not extra:
+    if args.full and world == 1 and not args.no_other_configs and not extra:
         other = []
         def block_config(name, data):
             tc, tdd = [], []
@@ -754,7 +810,7 @@ def main():
         alg = u_bytes + c_bytes                                     # U + C for compress, C + U for decompress
         pmc, pmc_src = traffic_profile()
         live = None
-        if world == 1 and not args.no_live_traffic and not os.environ.get("BENCH_NO_LIVE_TRAFFIC"):
+        if args.full and world == 1 and not args.no_live_traffic and not os.environ.get("BENCH_NO_LIVE_TRAFFIC"):
             live = live_traffic(nb, args.hash, args.config)      # two child runs under rocprofv3 --pmc: ~15 s each
         def roof(ms, kernel):
             a = alg / (ms * 1e-3) / 1e9

@@ -62,3 +62,42 @@ def test_pmc_rows_reads_rocprofv3_counter_csv(tmp_path):
     per = B.pmc_rows(str(tmp_path / "run"), "FETCH_SIZE")
     assert per == {"k_compress_lanes": [1000.0 * 1024, 3000.0 * 1024], "k_decompress_chains": [500.0 * 1024], "k_decompress_chains_list": [600.0 * 1024]}
     assert B.pmc_rows(str(tmp_path / "run"), "WRITE_SIZE") == {"k_compress_lanes": [7.0 * 1024]}
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every per-block vector in full, the bytes of a fixed seeded sample of blocks (compressed bytes past the block's length
+    written as 0), all float32, within 64 MB; the same inputs give the same files, and a sampled vector beyond DUMP_MAX_VECTOR_BLOCKS."""
+    import torch
+    B = _bench()
+    nb, stride = 200, 96
+    g = torch.Generator().manual_seed(7)
+    comp = torch.randint(0, 256, (nb * stride,), dtype=torch.uint8, generator=g)
+    out_len = torch.randint(1, stride + 1, (nb,), dtype=torch.int32, generator=g)
+    back = torch.randint(0, 256, (nb * B.BLOCK,), dtype=torch.uint8, generator=g)
+    status = torch.zeros(nb, dtype=torch.int32)
+    dlen = torch.full((nb,), B.BLOCK, dtype=torch.int32)
+    dst = torch.arange(nb, dtype=torch.int32) % 3
+    shapes = B.dump_outputs(str(tmp_path / "a"), comp, stride, out_len, status, back, dlen, dst)
+    k = min(B.DUMP_SAMPLE_BLOCKS, nb)
+    assert shapes == {"compressed_lengths": [nb], "compress_status": [nb], "compressed_bytes_sample": [k, stride],
+                      "decompressed_lengths": [nb], "decompress_status": [nb], "decompressed_bytes_sample": [k, B.BLOCK]}
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    assert all(v.dtype == np.float32 for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 * 10**6
+    assert np.array_equal(got["compressed_lengths"], out_len.numpy()) and np.array_equal(got["decompress_status"], dst.numpy())
+    assert np.array_equal(got["decompressed_lengths"], dlen.numpy()) and np.array_equal(got["compress_status"], status.numpy())
+    # every sampled row is one block, in block order; find which by its decompressed bytes
+    rows = back.numpy().reshape(nb, B.BLOCK)
+    idx = [int(np.flatnonzero((rows == r).all(axis=1))[0]) for r in got["decompressed_bytes_sample"].astype(np.uint8)]
+    assert idx == sorted(set(idx)) and len(idx) == k
+    cb = comp.numpy().reshape(nb, stride)
+    for row, b in zip(got["compressed_bytes_sample"], idx):
+        n = int(out_len[b])
+        assert np.array_equal(row[:n], cb[b, :n]) and not row[n:].any()
+    B.dump_outputs(str(tmp_path / "b"), comp, stride, out_len, status, back, dlen, dst)
+    for n in shapes:
+        assert np.array_equal(np.load(tmp_path / "b" / f"{n}.npy"), got[n]), n
+    monkeypatch.setattr(B, "DUMP_MAX_VECTOR_BLOCKS", 50)
+    shapes = B.dump_outputs(str(tmp_path / "c"), comp, stride, out_len, status, back, dlen, dst)
+    assert shapes["compressed_lengths"] == [50] and shapes["decompressed_bytes_sample"] == [k, B.BLOCK]
+    v = np.load(tmp_path / "c" / "decompress_status.npy")
+    assert set(v.tolist()) <= {0.0, 1.0, 2.0} and len(v) == 50

@@ -1,6 +1,6 @@
 """bench.py through its one-process-per-GPU path on the one-GPU box: launched by torch.distributed.run with ONE rank, so the RCCL process group, the
 barriers, the max-over-ranks timing and the length/status directory gather all execute (with N = 1 they are trivial, but they are the code the
-driver runs at N = 2, 4, 8).  A small batch, no CPU baseline, no PMC child runs."""
+driver runs at N = 2, 4, 8).  A small batch, --full for the configs[4] lines and per_rank, no CPU baseline, no PMC child runs."""
 import json
 import os
 import subprocess
@@ -19,8 +19,8 @@ def test_bench_runs_under_torch_distributed_run_with_one_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--blocks", "16384", "--no-cpu-baseline", "--no-live-traffic",
-           "--no-other-configs", "--config5-lines"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--blocks", "16384", "--full", "--no-cpu-baseline",
+           "--no-live-traffic", "--no-other-configs", "--config5-lines"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
