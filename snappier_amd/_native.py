@@ -132,5 +132,42 @@ def _load(path: str) -> C.CDLL:
     return L
 
 
+BUFFERS_PATH = os.path.join(HERE, "libsnappier_hip_buffers.so")
+BUFFERS_HEADER_PATH = os.path.join(HERE, "..", "include", "snappier_hip_buffers.h")
+PRODUCT_PATH = os.path.join(HERE, "libsnappier_hip.so")
+_buffers = None
+
+
+def buffers_declared_symbols() -> list[str]:
+    """Every function name declared in include/snappier_hip_buffers.h."""
+    with open(BUFFERS_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(snp_[a-z0-9_]+)\s*\(", text)))
+
+
+def buffers_lib() -> C.CDLL:
+    """libsnappier_hip_buffers.so (include/snappier_hip_buffers.h: buffers of any length, one block each).  It is linked against the PRODUCT
+    library and takes its contexts, so it is available only when lib() is the product library (not a variant under SNAPPIER_HIP_LIB, nor the
+    lab build)."""
+    global _buffers
+    if _buffers is None:
+        base = lib()
+        if os.path.realpath(base._name) != os.path.realpath(PRODUCT_PATH):
+            raise ImportError(f"libsnappier_hip_buffers.so is linked against {PRODUCT_PATH}; the loaded library is {base._name}")
+        if not os.path.exists(BUFFERS_PATH):
+            raise ImportError(f"{BUFFERS_PATH} is missing: build it with `python snappier_amd/build.py`")
+        L = C.CDLL(BUFFERS_PATH)
+        missing = [s for s in buffers_declared_symbols() if not hasattr(L, s)] if os.path.exists(BUFFERS_HEADER_PATH) else []
+        if missing:
+            raise ImportError(f"libsnappier_hip_buffers.so does not export: {missing}")
+        vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
+        L.snp_compress_buffers_workspace.restype = u64
+        L.snp_compress_buffers_workspace.argtypes = [u32, u32]
+        L.snp_compress_buffers_batch.restype = i32
+        L.snp_compress_buffers_batch.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+        _buffers = L
+    return _buffers
+
+
 def status_string(st: int) -> str:
     return lib().snp_status_string(st).decode()

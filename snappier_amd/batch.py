@@ -56,6 +56,45 @@ class BlockCodec:
         raise_for_status(st, self.ctx.handle)
         return out, out_off, out_len, status
 
+    def compress_buffers(self, data: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, out: torch.Tensor | None = None,
+                         out_off: torch.Tensor | None = None, out_cap: torch.Tensor | None = None, max_fragments: int | None = None,
+                         work: torch.Tensor | None = None):
+        """Buffers of ANY length, each one Snappy block (snp_compress_buffers_batch, libsnappier_hip_buffers.so): -> (out, out_off, out_len, status, result).
+
+        in_len holds u32 lengths (an int32 tensor's bits; lengths >= 2^31 are fine).  Defaults: out_cap = 32 + n + n // 6 + 1 + 5 per buffer
+        (snp_max_compressed_length, in int64 on the device), out_off = its exclusive cumsum, out sized to the sum, and max_fragments EXACT
+        (sum of ceil(n / 65536)).  Any default among out, max_fragments and work costs ONE synchronising read-back (the sums are fetched together);
+        a caller that passes all three -- and out_off / out_cap -- enqueues only.  out_len is int64, status int32, result the 2-element int64
+        d_result: [0] = fragments the batch needs, [1] = sum of out_len over the OK buffers."""
+        self._bind()
+        nb = in_len.numel()
+        n = in_len.to(torch.int64) & 0xFFFFFFFF
+        if out_cap is None:
+            out_cap = 32 + n + n // 6 + 1 + 5
+        if out_off is None:
+            out_off = torch.cumsum(out_cap, 0) - out_cap
+        if out is None or max_fragments is None:
+            sums = torch.stack([(out_off + out_cap).max() if nb else n.new_zeros(()), ((n + N.BLOCK_SIZE - 1) // N.BLOCK_SIZE).sum()]).tolist()
+            if out is None:
+                out = torch.empty(max(int(sums[0]), 1), dtype=torch.uint8, device=self.device)
+            if max_fragments is None:
+                max_fragments = int(sums[1])
+        BL = N.buffers_lib()
+        need = BL.snp_compress_buffers_workspace(nb, max_fragments)
+        if work is None:
+            work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if work.numel() < need:
+            raise ValueError(f"compress_buffers: work holds {work.numel()} bytes, snp_compress_buffers_workspace({nb}, {max_fragments}) = {need}")
+        if nb and data.numel() == 0:
+            data = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every buffer is empty: a valid pointer nothing reads)
+        out_len = torch.empty(nb, dtype=torch.int64, device=self.device)
+        status = torch.empty(nb, dtype=torch.int32, device=self.device)
+        result = torch.empty(2, dtype=torch.int64, device=self.device)
+        st = BL.snp_compress_buffers_batch(self.ctx.handle, _p(data), _p(in_off), _p(in_len), nb, max_fragments, _p(out), _p(out_off),
+                                           _p(out_cap), _p(out_len), _p(status), _p(work), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return out, out_off, out_len, status, result
+
     def decompress(self, comp: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, out: torch.Tensor,
                    out_off: torch.Tensor, out_cap: torch.Tensor):
         """-> (out_len, status)."""

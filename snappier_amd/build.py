@@ -1,6 +1,6 @@
 """Builds the gfx950 native libraries in-tree with hipcc (cross-compiles without a GPU).
 
-    python snappier_amd/build.py            # libsnappier_hip.so (+ libsnappier_datagen.so, bench/test helper)
+    python snappier_amd/build.py            # libsnappier_hip.so, libsnappier_hip_buffers.so (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
 
@@ -17,8 +17,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fco
 LIBS = {
     "libsnappier_hip.so": ["decode_chains.hip", "decompress.hip", "decompress_small.hip", "tag_index.hip", "compress_lanes.hip", "compress_win.hip", "crc32c.hip", "framing.hip", "frame_scan.hip",
                            "capi_ctx.hip", "capi_pool.hip", "capi_batch.hip", "capi_host.hip", "capi_frame.hip"],
+    # include/snappier_hip_buffers.h: buffers of any length, one block each -- an extension linked against the product library (its contexts)
+    "libsnappier_hip_buffers.so": ["buffers.hip", "capi_buffers.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
+LINK = {"libsnappier_hip_buffers.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"]}   # (built after libsnappier_hip.so: LIBS keeps its order)
 
 
 def _stale(target: str, sources: list[str]) -> bool:
@@ -37,7 +40,7 @@ def build_native(force: bool = False, verbose: bool = False) -> list[str]:
         target = os.path.join(HERE, lib)
         sources = [os.path.join(CSRC, s) for s in srcs]
         if force or _stale(target, sources):
-            cmd = [HIPCC] + FLAGS + sources + ["-o", target]
+            cmd = [HIPCC] + FLAGS + sources + ["-o", target] + LINK.get(lib, [])
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.run(cmd, check=True)

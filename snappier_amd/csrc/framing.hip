@@ -5,18 +5,6 @@
 
 namespace {
 
-// Copy len bytes with a whole 256-thread workgroup (no overlap).
-__device__ __forceinline__ void block_copy(u8* dst, const u8* src, u32 len, u32 tid)
-{
-    u32 k = tid * 16;
-    for (; k + 16 <= len; k += 256 * 16) {
-        snp_u128_unaligned w = *reinterpret_cast<const snp_u128_unaligned*>(src + k);
-        *reinterpret_cast<snp_u128_unaligned*>(dst + k) = w;
-    }
-    const u32 tail = len & ~15u;
-    if (tid < (len & 15u)) dst[tail + tid] = src[tail + tid];
-}
-
 __global__ __launch_bounds__(256) void k_gather(const u8* __restrict__ src, const u64* __restrict__ src_off,
                                                const u32* __restrict__ seg_len, u8* __restrict__ dst,
                                                const u64* __restrict__ dst_off, u32 nseg)

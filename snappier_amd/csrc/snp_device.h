@@ -13,6 +13,7 @@ typedef uint64_t u64;
 typedef int32_t i32;
 
 #define SNP_WAVE 64
+#define SNP_SCAN_TILE 1024u   // values per workgroup of the multi-workgroup prefix scans (buffers.hip)
 
 // The SNAPPIER_HIP_* environment variables are test and A/B knobs (kernel variants, layouts, thresholds): the product library reads NONE of them.
 // Only variant libraries built with -DSNAPPIER_HIP_DEBUG_ENV do (scripts/build_variant.sh, LAB=1: snappier_amd/variants/, loaded by A/B scripts on request; no test loads one).
@@ -77,6 +78,18 @@ __device__ __forceinline__ void wave_copy(u8* dst, const u8* src, u32 len, u32 l
     }
 #pragma clang loop vectorize(disable) unroll(disable)
     for (u32 k = done + lane; k < len; k += 64) dst[k] = src[k];   // (< 256 bytes: at most four trips -- not worth the unrolled code)
+}
+
+// Copy len bytes with a whole 256-thread workgroup (no overlap): 16 B per lane per step, then a byte tail.  All threads must call it.
+__device__ __forceinline__ void block_copy(u8* dst, const u8* src, u32 len, u32 tid)
+{
+    u32 k = tid * 16;
+    for (; k + 16 <= len; k += 256 * 16) {
+        snp_u128_unaligned w = *reinterpret_cast<const snp_u128_unaligned*>(src + k);
+        *reinterpret_cast<snp_u128_unaligned*>(dst + k) = w;
+    }
+    const u32 tail = len & ~15u;
+    if (tid < (len & 15u)) dst[tail + tid] = src[tail + tid];
 }
 
 // Framing mask  Crc32CAlgorithm.ApplyMask  (Snappier/Internal/Crc32CAlgorithm.cs:156-158)
