@@ -169,5 +169,40 @@ def buffers_lib() -> C.CDLL:
     return _buffers
 
 
+BUFFERS_DECOMPRESS_PATH = os.path.join(HERE, "libsnappier_hip_buffers_decompress.so")
+BUFFERS_DECOMPRESS_HEADER_PATH = os.path.join(HERE, "..", "include", "snappier_hip_buffers_decompress.h")
+_buffers_decompress = None
+
+
+def buffers_decompress_declared_symbols() -> list[str]:
+    """Every function name declared in include/snappier_hip_buffers_decompress.h."""
+    with open(BUFFERS_DECOMPRESS_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(snp_[a-z0-9_]+)\s*\(", text)))
+
+
+def buffers_decompress_lib() -> C.CDLL:
+    """libsnappier_hip_buffers_decompress.so (include/snappier_hip_buffers_decompress.h: device batch decompress that splits large blocks across
+    wavefronts).  Linked against the PRODUCT library, like buffers_lib()."""
+    global _buffers_decompress
+    if _buffers_decompress is None:
+        base = lib()
+        if os.path.realpath(base._name) != os.path.realpath(PRODUCT_PATH):
+            raise ImportError(f"libsnappier_hip_buffers_decompress.so is linked against {PRODUCT_PATH}; the loaded library is {base._name}")
+        if not os.path.exists(BUFFERS_DECOMPRESS_PATH):
+            raise ImportError(f"{BUFFERS_DECOMPRESS_PATH} is missing: build it with `python snappier_amd/build.py`")
+        L = C.CDLL(BUFFERS_DECOMPRESS_PATH)
+        missing = [s for s in buffers_decompress_declared_symbols() if not hasattr(L, s)]
+        if missing:
+            raise ImportError(f"libsnappier_hip_buffers_decompress.so does not export: {missing}")
+        vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
+        L.snp_decompress_buffers_workspace.restype = u64
+        L.snp_decompress_buffers_workspace.argtypes = [u32, u32]
+        L.snp_decompress_buffers_batch.restype = i32
+        L.snp_decompress_buffers_batch.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+        _buffers_decompress = L
+    return _buffers_decompress
+
+
 def status_string(st: int) -> str:
     return lib().snp_status_string(st).decode()

@@ -107,6 +107,32 @@ class BlockCodec:
         raise_for_status(st, self.ctx.handle)
         return out_len, status
 
+    def decompress_buffers(self, comp: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, out: torch.Tensor, out_off: torch.Tensor,
+                           out_cap: torch.Tensor, max_fragments: int | None = None, work: torch.Tensor | None = None):
+        """decompress() for batches that hold LARGE blocks (snp_decompress_buffers_batch, libsnappier_hip_buffers_decompress.so): the same
+        (out_len, status) -- plus result, the 4-element int64 d_result: [0] = fragments the blocks chosen for splitting need, [1] = blocks decoded
+        by fragments, [2] = chosen blocks that fell back to one wavefront, [3] = split blocks whose tag index took the look-back pass.
+        Default max_fragments: sum of ceil(out_cap / 65536) over the blocks, an upper bound on what any split block can need (declared <= out_cap);
+        it costs ONE synchronising read-back.  A caller that passes max_fragments and work enqueues only."""
+        self._bind()
+        nb = in_len.numel()
+        if max_fragments is None:
+            cap = out_cap.to(torch.int64) & 0xFFFFFFFF
+            max_fragments = min(int(((cap + N.BLOCK_SIZE - 1) // N.BLOCK_SIZE).sum().item()) if nb else 0, 0xFFFFFFFF)
+        BL = N.buffers_decompress_lib()
+        need = BL.snp_decompress_buffers_workspace(nb, max_fragments)
+        if work is None:
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        if work.numel() < need:
+            raise ValueError(f"decompress_buffers: work holds {work.numel()} bytes, snp_decompress_buffers_workspace({nb}, {max_fragments}) = {need}")
+        out_len = torch.empty(nb, dtype=torch.int32, device=self.device)
+        status = torch.empty(nb, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        st = BL.snp_decompress_buffers_batch(self.ctx.handle, _p(comp), _p(in_off), _p(in_len), nb, max_fragments, _p(out), _p(out_off),
+                                             _p(out_cap), _p(out_len), _p(status), _p(work), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return out_len, status, result
+
     def compact(self, data: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor):
         """Concatenate the blocks (snp_concat_batch): -> (stream tensor sized to the exact total, dst_off).  Needs the
         total on the host (one sync) to size the result."""

@@ -2,107 +2,18 @@
 // (SnappyCompressor.TryCompress  SnappyCompressor.cs:24-83: varint of the whole length, then one CompressFragment per 65536 bytes, back to back).
 // The fragments of all buffers are compressed in one launch of the existing compressor (capi_batch.hip, launch_compress with the varint off,
 // into a fixed-stride staging area); what is here is the plan before it and the emit after it:
-//   scan    exclusive prefix sums over u32 arrays, reduce-then-scan across workgroups (tiles of 1024 values): fragments per buffer
+//   scan    exclusive prefix sums, reduce-then-scan across workgroups (scan_tiles.h, tiles of 1024 values): fragments per buffer
 //           (ceil(len / 65536)) -> each buffer's first fragment; compressed length per fragment -> each fragment's place in its block
 //   plan    one thread per fragment slot: owning buffer (binary search over the first-fragment table), input range, staging offset;
 //           slots past the batch's fragments, and the fragments of buffers that do not fit in max_fragments, become empty fragments
 //   sizes   one thread per buffer: block size, status, out_len, the varint preamble, and the batch totals of d_result
 //   emit    one 256-thread workgroup per FRAGMENT (k_gather's copy), so a 4 GiB buffer is copied by 65 536 workgroups, not by one CU
 // Nothing here allocates or synchronises: the calls are capturable like the other _batch entry points.
-#include "snp_device.h"
+#include "scan_tiles.h"
 
 namespace {
 
-constexpr u32 kScanThreads = 256;
-constexpr u32 kScanItems = 4;
-constexpr u32 kScanTile = SNP_SCAN_TILE;                  // values per workgroup (snp_device.h: the workspace holds one tile sum per tile)
-static_assert(kScanTile == kScanThreads * kScanItems, "scan tile");
 constexpr u32 kNoOwner = 0xffffffffu;
-
-// the value scanned at position i: fragments of a buffer of src[i] bytes (FRAGS), or src[i] itself
-template <bool FRAGS>
-__device__ __forceinline__ u64 scan_value(const u32* __restrict__ src, u64 i)
-{
-    const u64 v = src[i];
-    return FRAGS ? (v + SNP_BLOCK_SIZE - 1) / SNP_BLOCK_SIZE : v;
-}
-
-// Exclusive scan of one u64 per thread over a 256-thread workgroup; *total = the workgroup's sum.  All threads must call it.
-__device__ __forceinline__ u64 wg_exclusive_scan(u64 v, u64* total)
-{
-    __shared__ u64 wave_sum[kScanThreads / SNP_WAVE];
-    const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    u64 x = v;
-    for (u32 d = 1; d < 64; d <<= 1) {
-        const u64 y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) wave_sum[wave] = x;
-    __syncthreads();
-    u64 before = 0, all = 0;
-    for (u32 w = 0; w < kScanThreads / SNP_WAVE; ++w) {
-        before += w < wave ? wave_sum[w] : 0;
-        all += wave_sum[w];
-    }
-    __syncthreads();                                                    // (wave_sum is reused by the next call)
-    *total = all;
-    return before + x - v;
-}
-
-// pass 1: the sum of each tile
-template <bool FRAGS>
-__global__ __launch_bounds__(kScanThreads) void k_scan_reduce(const u32* __restrict__ src, u32 n, u64* __restrict__ partial)
-{
-    const u64 base = static_cast<u64>(blockIdx.x) * kScanTile + threadIdx.x * kScanItems;
-    u64 s = 0;
-    for (u32 k = 0; k < kScanItems; ++k)
-        if (base + k < n) s += scan_value<FRAGS>(src, base + k);
-    u64 total;
-    (void)wg_exclusive_scan(s, &total);
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// pass 2 (one workgroup): tile sums -> tile offsets in place; dst[n] = the grand total.  result != nullptr: result[0] = the total,
-// result[1] = 0 (the sizes kernel adds to it later on the stream)
-__global__ __launch_bounds__(kScanThreads) void k_scan_partials(u64* __restrict__ partial, u32 ntiles, u64* __restrict__ dst_total,
-                                                               u64* __restrict__ result)
-{
-    u64 carry = 0;
-    for (u32 base = 0; base < ntiles; base += kScanThreads) {
-        const u32 i = base + threadIdx.x;
-        const u64 v = i < ntiles ? partial[i] : 0;
-        u64 total;
-        const u64 excl = wg_exclusive_scan(v, &total);
-        if (i < ntiles) partial[i] = carry + excl;
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        *dst_total = carry;
-        if (result) {
-            result[0] = carry;
-            result[1] = 0;
-        }
-    }
-}
-
-// pass 3: each tile scanned again, offset by its tile's place
-template <bool FRAGS>
-__global__ __launch_bounds__(kScanThreads) void k_scan_tiles(const u32* __restrict__ src, u32 n, const u64* __restrict__ partial,
-                                                            u64* __restrict__ dst)
-{
-    const u64 base = static_cast<u64>(blockIdx.x) * kScanTile + threadIdx.x * kScanItems;
-    u64 v[kScanItems], s = 0;
-    for (u32 k = 0; k < kScanItems; ++k) {
-        v[k] = base + k < n ? scan_value<FRAGS>(src, base + k) : 0;
-        s += v[k];
-    }
-    u64 total;
-    u64 run = partial[blockIdx.x] + wg_exclusive_scan(s, &total);
-    for (u32 k = 0; k < kScanItems; ++k) {
-        if (base + k < n) dst[base + k] = run;
-        run += v[k];
-    }
-}
 
 __global__ __launch_bounds__(256) void k_buffers_plan(const u64* __restrict__ in_off, const u32* __restrict__ in_len, u32 nbuffers,
                                                      const u64* __restrict__ first, u32 max_fragments, u64 stage_stride,
@@ -191,16 +102,6 @@ __global__ void k_buffers_result_empty(u64* result)
     if (threadIdx.x < 2) result[threadIdx.x] = 0;
 }
 
-template <bool FRAGS>
-hipError_t launch_scan(const u32* src, u32 n, u64* partial, u64* dst, u64* result, hipStream_t stream)
-{
-    const u32 ntiles = static_cast<u32>((static_cast<u64>(n) + kScanTile - 1) / kScanTile);
-    if (ntiles) hipLaunchKernelGGL((k_scan_reduce<FRAGS>), dim3(ntiles), dim3(kScanThreads), 0, stream, src, n, partial);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(kScanThreads), 0, stream, partial, ntiles, dst + n, result);
-    if (ntiles) hipLaunchKernelGGL((k_scan_tiles<FRAGS>), dim3(ntiles), dim3(kScanThreads), 0, stream, src, n, partial, dst);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" {
@@ -208,7 +109,7 @@ extern "C" {
 // first[0 .. nbuffers] = exclusive scan of ceil(in_len / 65536); result = {fragments needed, 0}
 hipError_t snp_launch_buffers_first(const u32* in_len, u32 nbuffers, u64* partial, u64* first, u64* result, hipStream_t stream)
 {
-    return launch_scan<true>(in_len, nbuffers, partial, first, result, stream);
+    return launch_scan(ScanFrags{in_len}, nbuffers, partial, first, result, stream);
 }
 
 hipError_t snp_launch_buffers_plan(const u64* in_off, const u32* in_len, u32 nbuffers, const u64* first, u32 max_fragments, u64 stage_stride,
@@ -223,7 +124,7 @@ hipError_t snp_launch_buffers_plan(const u64* in_off, const u32* in_len, u32 nbu
 // frag_scan[0 .. nfrag] = exclusive scan of the compressed lengths
 hipError_t snp_launch_buffers_frag_scan(const u32* comp_len, u32 nfrag, u64* partial, u64* frag_scan, hipStream_t stream)
 {
-    return launch_scan<false>(comp_len, nfrag, partial, frag_scan, nullptr, stream);
+    return launch_scan(ScanPlain{comp_len}, nfrag, partial, frag_scan, nullptr, stream);
 }
 
 hipError_t snp_launch_buffers_sizes(const u32* in_len, u32 nbuffers, const u64* first, u32 max_fragments, const u64* frag_scan, u8* out,

@@ -31,95 +31,9 @@
 // fragment decoder (k_decompress<.., FRAG = true>) then parses at most 4 KiB of tags before its fragment begins.
 // Anything that is not a well-formed stream ending exactly at (n, declared length) marks the table irregular and the
 // caller falls back to the single-wavefront decoder, which owns the error semantics.
-#include "snp_device.h"
+#include "tag_index_device.h"                  // build_table, walk_chunk, the candidate tables, scan_pass, fix_pass (shared with buffers_decode.hip)
 
 namespace {
-
-constexpr u32 kChunk = 16384;
-constexpr u32 kThreads = 1024;                    // one workgroup per CU (128 KiB of LDS): sixteen wavefronts hide the LDS latency of the pointer doubling
-constexpr u32 kSub = 4096;
-constexpr u32 kSubs = kChunk / kSub;
-constexpr u32 kRounds = 12;                       // a 4 KiB sub-chunk holds at most 2048 tags: 2^11 hops
-constexpr u64 kValid = 1ull << 63;
-constexpr u32 kBadIp = 0xffffffffu;               // entry: the stream is irregular from here on
-constexpr u32 kFar = 0xfffffffeu;                 // table: next-pointer not representable / tag truncated
-
-__device__ __forceinline__ u64 pack(u32 sum, u32 next) { return (static_cast<u64>(sum) << 32) | next; }
-
-// Steps 1a + 1b for the chunk at stream offset `base`: T[j] = (output bytes, first tag start at or after the end of j's sub-chunk).
-__device__ __forceinline__ void build_table(u64* T, u8* raw, const u8* __restrict__ src, const u32 n, const u64 base)
-{
-    // ---- 1a. the tag that would start at every position ----------------------------------------------------------
-    // the chunk's bytes (+ 8: a tag's trailer may reach into the next chunk; zeros past the end of the stream) come in once, 16 per thread, and
-    // every position reads its 8 from LDS (16 384 overlapping 8-byte gathers from global memory were a third of this function)
-    static_assert(kThreads * 16 == kChunk, "one 16-byte piece per thread");
-    {
-        const u64 p = base + threadIdx.x * 16u;
-        snp_u128_unaligned v = {{0, 0, 0, 0}};
-        if (p + 16 <= n) v = *reinterpret_cast<const snp_u128_unaligned*>(src + p);
-        else
-            for (u32 i = 0; i < 16 && p + i < n; ++i) reinterpret_cast<u8*>(&v)[i] = src[p + i];
-        *reinterpret_cast<snp_u128_unaligned*>(raw + threadIdx.x * 16u) = v;
-        if (threadIdx.x < 8) raw[kChunk + threadIdx.x] = base + kChunk + threadIdx.x < n ? src[base + kChunk + threadIdx.x] : u8{0};
-    }
-    __syncthreads();
-    for (u32 j = threadIdx.x; j < kChunk; j += kThreads) {
-        const u64 pos = base + j;
-        u64 e = pack(0, kFar);
-        if (pos < n) {
-            const u64 q = ld64u(raw + j);
-            const u32 c = static_cast<u32>(q) & 0xffu;
-            const u32 type = c & 3u;
-            const u32 hi6 = c >> 2;
-            const u32 extra = type == 0 ? (hi6 >= 60 ? hi6 - 59 : 0) : (type == 3 ? 4 : type);   // Constants.cs:42-76
-            const u32 b1234 = static_cast<u32>(q >> 8);
-            const u32 trailer = extra >= 4 ? b1234 : (b1234 & ((1u << (8 * extra)) - 1u));
-            u64 len;                                                      // output bytes
-            if (type == 0) len = hi6 >= 60 ? static_cast<u64>(trailer) + 1 : hi6 + 1;
-            else if (type == 1) len = (hi6 & 7u) + 4;
-            else len = hi6 + 1;
-            const u64 next = static_cast<u64>(j) + 1 + extra + (type == 0 ? len : 0);   // relative to the chunk
-            if (pos + 1 + extra <= n && next < kFar && len <= 0x7fffffffull)
-                e = pack(static_cast<u32>(len), static_cast<u32>(next));
-        }
-        T[j] = e;
-    }
-    __syncthreads();
-    // ---- 1b. pointer doubling inside each 4 KiB sub-chunk (in place: any value a reader sees is a valid jump) -----
-    for (u32 r = 0; r < kRounds; ++r) {
-#pragma unroll 4
-        for (u32 j = threadIdx.x; j < kChunk; j += kThreads) {
-            const u64 e = T[j];
-            const u32 nx = static_cast<u32>(e);
-            if (nx < kChunk && (nx / kSub) == (j / kSub) && base + nx < n) {   // the end of the stream is a terminal
-                const u64 e2 = T[nx];
-                const u64 sum = (e >> 32) + (e2 >> 32);
-                T[j] = pack(sum > 0x7fffffffull ? 0x80000000u : static_cast<u32>(sum), static_cast<u32>(e2));
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// Step 2's walk for one entry point: from (ip, op) through the chunk's sub-chunks; rec_ip / rec_op[sc] = the entry point of sub-chunk sc (sc >= 1)
-// as the look-back records it, [kSubs] = the entry of the next chunk.
-__device__ __forceinline__ void walk_chunk(const u64* T, const u32 n, const u64 base, u32 ip, u32 op, u32* rec_ip, u32* rec_op)
-{
-    for (u32 sc = 0; sc < kSubs; ++sc) {
-        rec_ip[sc] = ip;
-        rec_op[sc] = op;
-        const u64 sub_end = base + static_cast<u64>(sc + 1) * kSub;
-        if (ip == kBadIp || ip >= n || ip >= sub_end) continue;           // finished, irregular, or a literal jumps over this sub-chunk
-        const u64 e = T[ip - base];
-        const u32 nx = static_cast<u32>(e);
-        const u64 sum = static_cast<u64>(op) + (e >> 32);
-        if (nx >= kFar || base + nx > n || sum > 0x7fffffffull) { ip = kBadIp; continue; }
-        ip = static_cast<u32>(base + nx);
-        op = static_cast<u32>(sum);
-    }
-    rec_ip[kSubs] = ip;
-    rec_op[kSubs] = op;
-}
 
 __global__ __launch_bounds__(kThreads) void k_tag_index(const u8* __restrict__ src, u32 n, u32 hb, u32 nchunks,
                                                   u64* __restrict__ entries, u32* __restrict__ ticket, const u32* __restrict__ wanted)
@@ -165,28 +79,6 @@ __global__ __launch_bounds__(kThreads) void k_tag_index(const u8* __restrict__ s
         __hip_atomic_store(&entries[static_cast<u64>(k + 1) * kSubs], kValid | pack(op, ip), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-
-// ---- steps 2a / 2b: candidate entries per chunk, then one serial pass over the candidate tables ------------------------------------------
-constexpr u32 kMaxCand = 8;                       // distinct candidate entries a chunk may have (more: the fallback)
-constexpr u32 kProbe = 128;                       // walks from the chunk's first kProbe bytes define the next chunk's candidates
-constexpr u32 kWide = 0xffu;
-
-struct CandTable {                                // what step 2 would record for each candidate entry of one chunk; output bytes from the entry
-    u32 ncand;                                    // kWide: too many distinct landings
-    u32 key[kMaxCand];                            // stream position of the candidate entry
-    u32 ip[kMaxCand][kSubs];                      // [c][sc - 1] for sc = 1..3: sub-chunk entry points; [c][kSubs - 1]: the next chunk's entry
-    u32 op[kMaxCand][kSubs];
-    u32 nxt[kMaxCand];                            // which candidate of the NEXT chunk that entry is (its row there), kDone, or kFail
-};
-constexpr u32 kDone = kMaxCand;                   // the stream ended (entry = (n, op) from here on)
-constexpr u32 kFail = kMaxCand + 1;               // irregular from here on: the look-back kernel runs (and marks the table irregular)
-constexpr u32 kByPos = kMaxCand + 2;              // the next entry is the POSITION ip[c][kSubs - 1]: a landing beyond the next chunk, or in it but not
-                                                  // among its candidates -- the scan looks the position up when it gets there (k_tag_fix adds the row)
-struct CandHandoff {                              // chunk k - 1 -> chunk k: the candidates, then the flag (release / acquire)
-    u32 ready;
-    u32 ncand;
-    u32 key[kMaxCand];
-};
 
 __global__ __launch_bounds__(kThreads) void k_tag_cand(const u8* __restrict__ src, u32 n, u32 hb, u32 nchunks, CandTable* __restrict__ tables,
                                                  CandHandoff* __restrict__ hand, u32* __restrict__ ticket)
@@ -275,230 +167,6 @@ __global__ __launch_bounds__(kThreads) void k_tag_cand(const u8* __restrict__ sr
                 if (c < s_next_ncand && s_next_key[c] == out) nx = c;
         t->nxt[threadIdx.x] = nx;
     }
-}
-
-// ---- step 2b: the scan --------------------------------------------------------------------------------------------------------------------
-// The state between two chunks: a ROW of the next chunk's table, a POSITION further on (looked up when its chunk comes), the END of the
-// stream, FAILED (irregular), or PENDING (a position that is no candidate: k_tag_fix adds its row, the scan runs again).
-enum : u32 { kStRow = 0, kStPos = 1, kStEnd = 2, kStFail = 3, kStPend = 4 };
-struct ScanState {
-    u32 kind, v;                                  // v: row (kStRow) or stream position (kStPos)
-    u64 op;                                       // output bytes before the entry
-};
-struct ScanCtl {                                  // in the workspace's control words
-    u32 cand_ticket, look_back_ticket, fallback;  // (fallback: the look-back kernel is wanted)
-    u32 complete;                                 // the scan reached the end of the stream: the entries are final
-    u32 pending, pend_chunk, pend_ip, pend_op;    // a landing that needs a row (k_tag_fix)
-    u32 cached;                                   // the run functions of the first pass are in the workspace (k_tag_fix only ADDS rows: they stay valid,
-};                                                //  except where a run stopped at a pending landing)
-struct RunCache {                                 // [thread][row]
-    u8 kind[kThreads][kMaxCand];
-    u32 v[kThreads][kMaxCand];
-    u64 op[kThreads][kMaxCand];
-};
-
-// One chunk.  entries != nullptr: the replay -- writes the chunk's entries and files the pending request.
-__device__ __forceinline__ void scan_step(ScanState& s, const u32 k, const CandTable* __restrict__ tables, const u32 n, const u32 hb,
-                                          u64* __restrict__ entries, ScanCtl* __restrict__ ctl)
-{
-    if (s.kind == kStFail || s.kind == kStPend) return;
-    if (s.op > 0x7fffffffull) { s.kind = kStFail; return; }
-    u64* const e = entries ? entries + static_cast<u64>(k) * kSubs : nullptr;
-    const u32 op = static_cast<u32>(s.op);
-    if (s.kind == kStEnd) {
-        if (e) for (u32 sc = 0; sc < kSubs; ++sc) e[sc] = kValid | pack(op, n);
-        return;
-    }
-    const u64 end = hb + static_cast<u64>(k + 1) * kChunk;
-    const CandTable& t = tables[k];
-    if (s.kind == kStPos) {
-        if (s.v >= end) {                                                // a literal jumps over this chunk
-            if (e) for (u32 sc = 0; sc < kSubs; ++sc) e[sc] = kValid | pack(op, s.v);
-            return;
-        }
-        u32 row = kMaxCand;
-        if (t.ncand != kWide)
-            for (u32 c = 0; c < kMaxCand; ++c)
-                if (c < t.ncand && t.key[c] == s.v) row = c;
-        if (row == kMaxCand) {
-            if (ctl) { ctl->pend_chunk = k; ctl->pend_ip = s.v; ctl->pend_op = op; ctl->pending = 1; }
-            s.kind = kStPend;
-            return;
-        }
-        s.kind = kStRow;
-        s.v = row;
-    }
-    if (t.ncand == kWide || s.v >= t.ncand) { s.kind = kStFail; return; }   // (cannot happen: a row comes from nxt or from the lookup above)
-    const u32 row = s.v;
-    if (e) e[0] = kValid | pack(op, t.key[row]);
-    for (u32 sc = 1; sc < kSubs; ++sc) {
-        const u64 sum = s.op + t.op[row][sc - 1];
-        if (t.ip[row][sc - 1] == kBadIp || sum > 0x7fffffffull) { s.kind = kStFail; return; }
-        if (e) e[sc] = kValid | pack(static_cast<u32>(sum), t.ip[row][sc - 1]);
-    }
-    s.op += t.op[row][kSubs - 1];
-    const u32 nx = t.nxt[row];
-    if (nx < kMaxCand) { s.kind = kStRow; s.v = nx; }
-    else if (nx == kDone) s.kind = kStEnd;
-    else if (nx == kByPos) { s.kind = kStPos; s.v = t.ip[row][kSubs - 1]; }
-    else s.kind = kStFail;
-}
-
-// One workgroup.  A run of chunks is a function on <= 8 rows: every thread evaluates its run for each row; thread 0 chains the runs (a run entered
-// by POSITION is evaluated then and there: chunks a literal jumps over cost no memory access); every thread replays its run from its true
-// entry state, writing the entries.  `last`: no k_tag_fix follows -- a pending landing means the look-back kernel.
-struct ScanLds {                                  // (carved out of the workgroup's LDS pool: the table of k_tag_fix lives there between scans)
-    u8 r_kind[kThreads][kMaxCand];
-    u32 r_v[kThreads][kMaxCand];
-    u64 r_op[kThreads][kMaxCand];
-    u8 in_kind[kThreads];
-    u32 in_v[kThreads];
-    u64 in_op[kThreads];
-};
-__device__ __forceinline__ void scan_pass(const CandTable* __restrict__ tables, u32 n, u32 hb, u32 nchunks, u64* __restrict__ entries,
-                                          ScanCtl* __restrict__ ctl, RunCache* __restrict__ cache, const bool last, ScanLds& L, u32& s_final)
-{
-    auto& r_kind = L.r_kind;
-    auto& r_v = L.r_v;
-    auto& r_op = L.r_op;
-    auto& in_kind = L.in_kind;
-    auto& in_v = L.in_v;
-    auto& in_op = L.in_op;
-    const u32 per = (nchunks + kThreads - 1) / kThreads;
-    const u32 k0 = min(threadIdx.x * per, nchunks), k1 = min(k0 + per, nchunks);
-    const bool cached = __hip_atomic_load(&ctl->cached, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-    for (u32 r = 0; r < kMaxCand; ++r) {
-        ScanState s{kStRow, r, 0};
-        if (cached && cache->kind[threadIdx.x][r] != kStPend) {          // (a later pass: only what stopped at a pending landing is evaluated again)
-            s.kind = cache->kind[threadIdx.x][r];
-            s.v = cache->v[threadIdx.x][r];
-            s.op = cache->op[threadIdx.x][r];
-        } else {
-            if (k0 < k1 && (tables[k0].ncand == kWide || r >= tables[k0].ncand)) s.kind = kStFail;   // (no such row: never selected)
-            for (u32 k = k0; k < k1 && s.kind != kStFail && s.kind != kStPend; ++k) scan_step(s, k, tables, n, hb, nullptr, nullptr);
-            cache->kind[threadIdx.x][r] = static_cast<u8>(s.kind);
-            cache->v[threadIdx.x][r] = s.v;
-            cache->op[threadIdx.x][r] = s.op;
-        }
-        r_kind[threadIdx.x][r] = static_cast<u8>(s.kind);
-        r_v[threadIdx.x][r] = s.v;
-        r_op[threadIdx.x][r] = s.op;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ScanState s{kStRow, 0, 0};                                       // chunk 0 has one candidate: the first tag after the preamble
-        for (u32 t = 0; t < kThreads; ++t) {
-            in_kind[t] = static_cast<u8>(s.kind);
-            in_v[t] = s.v;
-            in_op[t] = s.op;
-            const u32 a0 = min(t * per, nchunks), a1 = min(a0 + per, nchunks);
-            if (s.kind == kStRow && a0 < a1) {
-                const u32 r = s.v;
-                s.kind = r_kind[t][r];
-                s.v = r_v[t][r];
-                s.op += r_op[t][r];
-            } else if (s.kind == kStPos) {
-                for (u32 k = a0; k < a1; ++k) scan_step(s, k, tables, n, hb, nullptr, nullptr);
-            }
-        }
-        s_final = s.kind;
-    }
-    __syncthreads();
-    ScanState s{in_kind[threadIdx.x], in_v[threadIdx.x], in_op[threadIdx.x]};
-    for (u32 k = k0; k < k1; ++k) scan_step(s, k, tables, n, hb, entries, ctl);
-    if (k0 < k1 && k1 == nchunks && s.kind == kStEnd) entries[static_cast<u64>(nchunks) * kSubs] = kValid | pack(static_cast<u32>(s.op), n);
-    if (threadIdx.x == 0) {
-        ctl->cached = 1;
-        if (s_final == kStEnd) ctl->complete = 1;
-        else if (s_final != kStPend || last) ctl->fallback = 1;          // irregular (or the stream does not end with its last chunk); or out of passes
-    }
-    __syncthreads();
-}
-
-// ---- step 2c: a landing that was no candidate gets its row ---------------------------------------------------------------------------------------
-// One workgroup follows the true chain from the pending landing: a tag that leaves its chunk by itself (a literal longer than what is left of the
-// chunk: the incompressible fragments) gets its row from its own bytes; anything else from the chunk's table, built here; until the chain lands on
-// a candidate again (it has merged with the walks the candidates came from) or the budget of this pass is spent.
-constexpr u32 kFixBudget = 4096;                  // landings one pass may give a row
-constexpr u32 kFixPasses = 512;                   // passes at most (each ends where the chain rejoins the candidates: one per incompressible region)
-constexpr u32 kChunksPerPass = 417;               // a pass costs ~0.35 ms, the look-back kernel 0.84 us per chunk: more passes than chunks / 417 and it is cheaper
-struct FixLds {
-    u64 T[kChunk];
-    __attribute__((aligned(16))) u8 raw[kChunk + 16];
-};
-struct FixVars { u32 k, ip, go, far, next, len; };
-__device__ __forceinline__ void fix_pass(const u8* __restrict__ src, u32 n, u32 hb, CandTable* __restrict__ tables, ScanCtl* __restrict__ ctl,
-                                         FixLds& F, FixVars& V)
-{
-    u64* const T = F.T;
-    u8* const s_raw = F.raw;
-    u32 &s_k = V.k, &s_ip = V.ip, &s_go = V.go, &s_far = V.far, &s_next = V.next, &s_len = V.len;
-    if (threadIdx.x == 0) { s_k = ctl->pend_chunk; s_ip = ctl->pend_ip; s_go = 1; }
-    __syncthreads();
-    for (u32 it = 0; it < kFixBudget; ++it) {
-        if (!s_go) break;
-        const u32 k = s_k, ip = s_ip;
-        const u64 base = hb + static_cast<u64>(k) * kChunk, end = base + kChunk;
-        // the tag at ip, from its own bytes: does it leave the chunk by itself?
-        if (threadIdx.x == 0) {
-            u64 q = 0;
-            for (u32 i = 0; i < 8 && ip + i < n; ++i) q |= static_cast<u64>(src[ip + i]) << (8 * i);
-            const u32 c = static_cast<u32>(q) & 0xffu, type = c & 3u, hi6 = c >> 2;
-            const u32 extra = type == 0 ? (hi6 >= 60 ? hi6 - 59 : 0) : (type == 3 ? 4 : type);
-            const u32 b1234 = static_cast<u32>(q >> 8);
-            const u32 trailer = extra >= 4 ? b1234 : (b1234 & ((1u << (8 * extra)) - 1u));
-            const u64 len = type == 0 ? (hi6 >= 60 ? static_cast<u64>(trailer) + 1 : hi6 + 1) : 0;
-            const u64 next = static_cast<u64>(ip) + 1 + extra + len;
-            s_far = type == 0 && static_cast<u64>(ip) + 1 + extra <= n && next >= end && next <= n && len <= 0x7fffffffull;
-            s_next = static_cast<u32>(next);
-            s_len = static_cast<u32>(len);
-        }
-        __syncthreads();
-        u32 rip[kSubs + 1], rop[kSubs + 1];
-        if (s_far) {                                                     // walk_chunk's record for a single tag that leaves the chunk
-            for (u32 sc = 0; sc <= kSubs; ++sc) {
-                const bool after = sc == kSubs || base + static_cast<u64>(sc) * kSub > ip;
-                rip[sc] = after ? s_next : ip;
-                rop[sc] = after ? s_len : 0u;
-            }
-        } else {
-            build_table(T, s_raw, src, n, base);
-            walk_chunk(T, n, base, ip, 0u, rip, rop);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            CandTable& t = tables[k];
-            u32 r = t.ncand == kWide ? 0u : t.ncand;
-            if (r >= kMaxCand) {
-                ctl->fallback = 1;                                       // no room for another row
-                s_go = 0;
-            } else {
-                t.key[r] = ip;
-                for (u32 sc = 1; sc <= kSubs; ++sc) {
-                    t.ip[r][sc - 1] = rip[sc];
-                    t.op[r][sc - 1] = rop[sc];
-                }
-                const u32 out = rip[kSubs];
-                u32 nx = out == kBadIp ? kFail : out == n ? kDone : kByPos;
-                bool joined = nx != kByPos;                              // (the end, or irregular: nothing more to add)
-                u32 ko = 0;
-                if (nx == kByPos) {
-                    ko = static_cast<u32>((out - hb) / kChunk);
-                    const CandTable& o = tables[ko];
-                    if (o.ncand != kWide)
-                        for (u32 c = 0; c < kMaxCand; ++c)
-                            if (c < o.ncand && o.key[c] == out) { joined = true; if (ko == k + 1) nx = c; }
-                }
-                t.nxt[r] = nx;
-                t.ncand = r + 1;
-                if (joined) s_go = 0;
-                else { s_k = ko; s_ip = out; }
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) ctl->pending = 0;
-    __syncthreads();
 }
 
 // One workgroup: scan; while a landing is pending: give it (and what follows it, up to the rejoin) rows, scan again.
