@@ -16,6 +16,15 @@ BAD = 0xFFFFFFFF
 MAXC = 8
 WIDE = 0xFF
 DONE, FAIL, BYPOS = MAXC, MAXC + 1, MAXC + 2
+# the device's sizes and pass budget (tag_index_device.h: kChunk, kSub, kProbe, kFixPasses, kChunksPerPass)
+DEVICE_CHUNK, DEVICE_SUB, DEVICE_PROBE = 16384, 4096, 128
+FIX_PASSES, CHUNKS_PER_PASS = 512, 417
+
+
+def device_fix_passes(nchunks: int) -> int:
+    """Fix passes the kernels allow a stream of `nchunks` chunks before the scan gives up (k_tag_scan / k_bd_tag_scan:
+    min(kFixPasses, max(1, nchunks / kChunksPerPass))): run(max_passes=this) reaches the kernels' verdict."""
+    return min(FIX_PASSES, max(1, nchunks // CHUNKS_PER_PASS))
 
 
 def decode_tag(s: bytes, p: int):

@@ -292,7 +292,7 @@ def test_error_taxonomy_through_every_small_block_layout(layout):
 
 
 def test_context_options_pin_layouts_without_changing_results():
-    """snp_ctx_set_option (include/snappier_hip.h): decode layout, small-block thresholds, compress layout, probe cap -- set through
+    """snp_ctx_set_option (include/snappier_hip.h): decode layout, small-block thresholds, compress layout, probe cap, LDS throttle -- set through
     the C-ABI between calls on ONE context, alternating block sizes (the workload whose policy would otherwise come from the previous
     batch): every setting returns the oracle's bytes; bad values are rejected and change nothing."""
     N = S._native
@@ -327,6 +327,22 @@ def test_context_options_pin_layouts_without_changing_results():
         torch.cuda.synchronize()
         assert int((dst != 0).sum()) == 0 and np.array_equal(dlen.cpu().numpy(), lens)
         assert np.array_equal(back.cpu().numpy()[: data.size], data), layout
+    # SNP_OPT_DECODE_LDS_THROTTLE: every value the setter accepts launches (the decoders' own LDS included) and changes no result
+    for bad in (-1, 65537):
+        with pytest.raises(ValueError):
+            ctx.set_option(N.OPT_DECODE_LDS_THROTTLE, bad)
+    assert ctx.get_option(N.OPT_DECODE_LDS_THROTTLE) == 0
+    for throttle in (256, 300, 32768, 65536):
+        ctx.set_option(N.OPT_DECODE_LDS_THROTTLE, throttle)
+        assert ctx.get_option(N.OPT_DECODE_LDS_THROTTLE) == throttle // 256 * 256
+        for layout in (0, 1, 2, 6):
+            ctx.set_option(N.OPT_DECODE_LAYOUT, layout)
+            back.zero_()
+            dlen, dst = cd.decompress(out, out_off, out_len, back, dev(off), dev(lens))
+            torch.cuda.synchronize()
+            assert int((dst != 0).sum()) == 0 and np.array_equal(dlen.cpu().numpy(), lens), (throttle, layout)
+            assert np.array_equal(back.cpu().numpy()[: data.size], data), (throttle, layout)
+    ctx.set_option(N.OPT_DECODE_LDS_THROTTLE, 0)
     ctx.set_option(N.OPT_COMPRESS_LAYOUT, 0)
     ctx.set_option(N.OPT_DECODE_LAYOUT, 0)
 

@@ -1,12 +1,14 @@
 """The tag index of one large block (snappier_amd/csrc/tag_index.hip) as a CPU model (tests/tag_index_model.py): candidate entries per chunk,
 rows, a scan that carries rows or positions, rows added for landings that were no candidates -- against the serial tag walk of the
 reference (SnappyDecompressor.cs:184-347).  Small chunks (256 / 64 bytes) so that literals longer than a chunk, streams that end inside a
-sub-chunk and many incompressible regions all occur in a few KiB.  The -m gpu tests (tests/test_gpu_big_blocks.py) run the kernels."""
+sub-chunk and many incompressible regions all occur in a few KiB; and at the kernels' own sizes and pass budget, the verdict of each shaped
+stream of tests/shaped_streams.py.  The -m gpu tests (tests/test_gpu_big_blocks.py, tests/test_gpu_buffers_stress.py) run the kernels."""
 import numpy as np
 import pytest
 
 import oracle as O
-from tag_index_model import TagIndexModel, reference_entries
+import shaped_streams as SS
+from tag_index_model import DEVICE_CHUNK, DEVICE_PROBE, DEVICE_SUB, TagIndexModel, device_fix_passes, reference_entries
 
 
 def _stream(data: bytes):
@@ -90,3 +92,31 @@ def test_more_landings_than_rows_give_up_cleanly():
     r = m.run(max_passes=400)
     want, final = reference_entries(z, hb, 128, 32)
     assert r[0] == "fail" or (r[1] == want and r[2] == final)
+
+
+def test_device_pass_budget():
+    assert [device_fix_passes(n) for n in (1, 416, 833, 834, 1250, 1251, 417 * 512, 10 ** 7)] == [1, 1, 1, 2, 2, 3, 512, 512]
+
+
+@pytest.mark.parametrize("shape", SS.SHAPES)
+def test_shaped_streams_give_their_look_back_verdict_at_device_sizes(shape):
+    """The decision the device tests of the batched call assert (tests/test_gpu_buffers_stress.py), read from the code and confirmed here:
+    the model at the kernels' chunk, sub-chunk and probe sizes, with their pass budget, is done (no look-back pass) or out of passes (the
+    look-back pass) -- and a stream of >= 85 % of its output never gets a scan at all."""
+    z, data = SS.stream(shape), SS.raw(shape)
+    hb = SS.preamble_bytes(z)
+    assert len(data) < (8 << 20) and O.decompress(z) == data
+    nchunks = (len(z) - hb + DEVICE_CHUNK - 1) // DEVICE_CHUNK
+    if SS.look_back_only(z, len(data)):
+        assert SS.LOOK_BACK[shape] == 1 and shape == "S3"
+        return
+    m = TagIndexModel(z, hb, DEVICE_CHUNK, DEVICE_SUB, DEVICE_PROBE)
+    r = m.run(max_passes=device_fix_passes(nchunks))
+    want, final = reference_entries(z, hb, DEVICE_CHUNK, DEVICE_SUB)
+    if SS.LOOK_BACK[shape] == 0:
+        assert r[0] == "done" and r[1] == want and r[2] == final == (len(z), len(data)), shape
+        assert m.passes == (0 if shape == "S1" else 1), (shape, m.passes)        # S1: candidates suffice; S2, S4: one fix pass
+    else:
+        assert r[0] == "fail" and m.passes == device_fix_passes(nchunks) == 1, (shape, r[0], m.passes)
+        more = TagIndexModel(z, hb, DEVICE_CHUNK, DEVICE_SUB, DEVICE_PROBE).run(max_passes=8)
+        assert more[0] == "done" and more[1] == want, shape                     # out of passes, not an irregular stream
