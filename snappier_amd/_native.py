@@ -204,5 +204,44 @@ def buffers_decompress_lib() -> C.CDLL:
     return _buffers_decompress
 
 
+FRAME_BUFFERS_PATH = os.path.join(HERE, "libsnappier_hip_frame_buffers.so")
+FRAME_BUFFERS_HEADER_PATH = os.path.join(HERE, "..", "include", "snappier_hip_frame_buffers.h")
+_frame_buffers = None
+
+
+def frame_buffers_declared_symbols() -> list[str]:
+    """Every function name declared in include/snappier_hip_frame_buffers.h."""
+    with open(FRAME_BUFFERS_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(snp_[a-z0-9_]+)\s*\(", text)))
+
+
+def frame_buffers_lib() -> C.CDLL:
+    """libsnappier_hip_frame_buffers.so (include/snappier_hip_frame_buffers.h: device batch encode and decode of many framed streams).  Linked
+    against the PRODUCT library, like buffers_lib()."""
+    global _frame_buffers
+    if _frame_buffers is None:
+        base = lib()
+        if os.path.realpath(base._name) != os.path.realpath(PRODUCT_PATH):
+            raise ImportError(f"libsnappier_hip_frame_buffers.so is linked against {PRODUCT_PATH}; the loaded library is {base._name}")
+        if not os.path.exists(FRAME_BUFFERS_PATH):
+            raise ImportError(f"{FRAME_BUFFERS_PATH} is missing: build it with `python snappier_amd/build.py`")
+        L = C.CDLL(FRAME_BUFFERS_PATH)
+        missing = [s for s in frame_buffers_declared_symbols() if not hasattr(L, s)]
+        if missing:
+            raise ImportError(f"libsnappier_hip_frame_buffers.so does not export: {missing}")
+        vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
+        L.snp_frame_encode_buffers_workspace.restype = u64
+        L.snp_frame_encode_buffers_workspace.argtypes = [u32, u32]
+        L.snp_frame_encode_buffers_batch.restype = i32
+        L.snp_frame_encode_buffers_batch.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+        L.snp_frame_decode_buffers_workspace.restype = u64
+        L.snp_frame_decode_buffers_workspace.argtypes = [u32, u32, u32]
+        L.snp_frame_decode_buffers_batch.restype = i32
+        L.snp_frame_decode_buffers_batch.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+        _frame_buffers = L
+    return _frame_buffers
+
+
 def status_string(st: int) -> str:
     return lib().snp_status_string(st).decode()

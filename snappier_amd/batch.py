@@ -173,6 +173,86 @@ class BlockCodec:
         raise_for_status(st, self.ctx.handle)
         return out, written
 
+    def frame_encode_buffers(self, data: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, out: torch.Tensor | None = None,
+                             out_off: torch.Tensor | None = None, out_cap: torch.Tensor | None = None, max_chunks: int | None = None,
+                             work: torch.Tensor | None = None):
+        """Many framed streams in one call (snp_frame_encode_buffers_batch, libsnappier_hip_frame_buffers.so): -> (out, out_off, out_len, status, result).
+
+        Buffer b is data[in_off[b] .. +in_len[b]) (int64 offsets and lengths) and becomes what frame_encode gives for it alone.  Defaults:
+        out_cap = snp_frame_max_encoded_length per buffer (10 + 8 * chunks + n, in int64 on the device), out_off = its exclusive cumsum, out
+        sized to the sum, and max_chunks EXACT (sum of ceil(n / 65536)).  Any default among out, max_chunks and work costs ONE synchronising
+        read-back (the sums are fetched together); a caller that passes all three -- and out_off / out_cap -- enqueues only.  out_len is
+        int64, status int32, result the 2-element int64 d_result: [0] = chunk slots the batch needs, [1] = sum of out_len over the OK buffers."""
+        self._bind()
+        nb = in_len.numel()
+        n = in_len.to(torch.int64)
+        chunks = (n + N.BLOCK_SIZE - 1) // N.BLOCK_SIZE
+        if out_cap is None:
+            out_cap = 10 + 8 * chunks + n
+        if out_off is None:
+            out_off = torch.cumsum(out_cap, 0) - out_cap
+        if out is None or max_chunks is None:
+            sums = torch.stack([(out_off + out_cap).max() if nb else n.new_zeros(()), chunks.sum()]).tolist()
+            if out is None:
+                out = torch.empty(max(int(sums[0]), 1), dtype=torch.uint8, device=self.device)
+            if max_chunks is None:
+                max_chunks = int(sums[1])
+        FL = N.frame_buffers_lib()
+        need = FL.snp_frame_encode_buffers_workspace(nb, max_chunks)
+        if work is None:
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        if work.numel() < need:
+            raise ValueError(f"frame_encode_buffers: work holds {work.numel()} bytes, snp_frame_encode_buffers_workspace({nb}, {max_chunks}) = {need}")
+        if nb and data.numel() == 0:
+            data = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every buffer is empty: a valid pointer nothing reads)
+        out_len = torch.empty(nb, dtype=torch.int64, device=self.device)
+        status = torch.empty(nb, dtype=torch.int32, device=self.device)
+        result = torch.empty(2, dtype=torch.int64, device=self.device)
+        st = FL.snp_frame_encode_buffers_batch(self.ctx.handle, _p(data), _p(in_off), _p(in_len), nb, max_chunks, _p(out), _p(out_off),
+                                               _p(out_cap), _p(out_len), _p(status), _p(work), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return out, out_off, out_len, status, result
+
+    def frame_decode_buffers(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, out: torch.Tensor, out_off: torch.Tensor,
+                             out_cap: torch.Tensor, max_chunks: int | None = None, max_spans: int | None = None, work: torch.Tensor | None = None):
+        """Many framed streams in one call (snp_frame_decode_buffers_batch, libsnappier_hip_frame_buffers.so): -> (out_len, status, result).
+
+        Stream b is framed[in_off[b] .. +in_len[b]) and decodes into out[out_off[b] .. +out_cap[b]) (int64 offsets, lengths and capacities);
+        status[b] / out_len[b] are what frame_decode gives for it alone.  result is the 4-element int64 d_result: [0] = chunk slots the walked
+        streams need, [1] = sum of out_len over the OK streams, [2] = span slots needed, [3] = spans the resolver walked on the spot.
+        Default max_spans: EXACT (sum of ceil(in_len / 2^20)), ONE synchronising read-back.  Default max_chunks: a first call with max_chunks = 0
+        (it walks every stream and decodes nothing), then a synchronising read of its d_result[0].  A caller that passes max_chunks, max_spans
+        and work enqueues only."""
+        self._bind()
+        ns = in_len.numel()
+        FL = N.frame_buffers_lib()
+        if max_spans is None:
+            n = in_len.to(torch.int64)
+            max_spans = int(((n + (1 << 20) - 1) >> 20).sum().item()) if ns else 0
+        if ns and framed.numel() == 0:
+            framed = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every stream is empty: a valid pointer nothing reads)
+        if ns and out.numel() == 0:
+            out = torch.empty(16, dtype=torch.uint8, device=self.device)      # (nothing to write: a valid pointer)
+        out_len = torch.empty(ns, dtype=torch.int64, device=self.device)
+        status = torch.empty(ns, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+
+        def call(mc: int, w: torch.Tensor | None):
+            need = FL.snp_frame_decode_buffers_workspace(ns, mc, max_spans)
+            if w is None:
+                w = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+            if w.numel() < need:
+                raise ValueError(f"frame_decode_buffers: work holds {w.numel()} bytes, snp_frame_decode_buffers_workspace({ns}, {mc}, {max_spans}) = {need}")
+            st = FL.snp_frame_decode_buffers_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, mc, max_spans, _p(out), _p(out_off),
+                                                   _p(out_cap), _p(out_len), _p(status), _p(w), _p(result))
+            raise_for_status(st, self.ctx.handle)
+
+        if max_chunks is None:
+            call(0, None)
+            max_chunks = min(int(result[0].item()), 0xFFFFFFFF)
+        call(max_chunks, work)
+        return out_len, status, result
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()

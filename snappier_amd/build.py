@@ -1,6 +1,7 @@
 """Builds the gfx950 native libraries in-tree with hipcc (cross-compiles without a GPU).
 
-    python snappier_amd/build.py            # libsnappier_hip.so, libsnappier_hip_buffers.so, libsnappier_hip_buffers_decompress.so (+ libsnappier_datagen.so, bench/test helper)
+    python snappier_amd/build.py            # libsnappier_hip.so, libsnappier_hip_buffers.so, libsnappier_hip_buffers_decompress.so,
+                                            # libsnappier_hip_frame_buffers.so (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
 
@@ -21,10 +22,13 @@ LIBS = {
     "libsnappier_hip_buffers.so": ["buffers.hip", "capi_buffers.hip"],
     # include/snappier_hip_buffers_decompress.h: device batch decompress that splits large blocks across wavefronts -- the same kind of extension
     "libsnappier_hip_buffers_decompress.so": ["buffers_decode.hip"],
+    # include/snappier_hip_frame_buffers.h: device batch encode / decode of many framed streams -- the same kind of extension
+    "libsnappier_hip_frame_buffers.so": ["frame_buffers.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 LINK = {"libsnappier_hip_buffers.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"],
-        "libsnappier_hip_buffers_decompress.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"]}   # (built after libsnappier_hip.so: LIBS keeps its order)
+        "libsnappier_hip_buffers_decompress.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"],
+        "libsnappier_hip_frame_buffers.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"]}   # (built after libsnappier_hip.so: LIBS keeps its order)
 
 
 def _stale(target: str, sources: list[str]) -> bool:

@@ -6,7 +6,8 @@
 //     capi_host.hip    the host-pointer calls: snp_try_compress / snp_try_decompress (+ segments), snp_crc32c
 //     capi_frame.hip   framing orchestration: snp_frame_encode* / snp_frame_decode*
 //     capi_buffers.hip snp_compress_buffers_batch: buffers of any length, one block each (plan / scan / emit kernels in buffers.hip) -- these two
-//                      form libsnappier_hip_buffers.so (include/snappier_hip_buffers.h), linked against libsnappier_hip.so
+//                      form libsnappier_hip_buffers.so (include/snappier_hip_buffers.h), linked against libsnappier_hip.so; buffers_decode.hip and
+//                      frame_buffers.hip form two more such extensions (snappier_hip_buffers_decompress.h, snappier_hip_frame_buffers.h)
 // No codec arithmetic happens on the host: every byte of compress / decompress / CRC work is done by the gfx950 kernels in compress_lanes.hip,
 // compress_win.hip, decode_chains.hip, decompress.hip, decompress_small.hip, tag_index.hip, crc32c.hip, framing.hip, frame_scan.hip, buffers.hip.
 // There is no CPU fallback -- without a HIP device snp_ctx_create fails with SNP_ERR_DEVICE.
