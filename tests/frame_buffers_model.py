@@ -175,8 +175,27 @@ def follow_chain(s: bytes, start: int, span_end: int):
     return ip, dec, nd, stop
 
 
+def shape_prefilter(s: bytes, lo: int, hi: int) -> np.ndarray:
+    """Positions p in [lo, hi) that pass chunk_shape's type and size rules (a superset of its answer, in NumPy): -> sorted int64 positions."""
+    n = len(s)
+    hi = min(hi, n - 7)                                                 # chunk_shape: n - p >= 8
+    if hi <= lo:
+        return np.zeros(0, dtype=np.int64)
+    w = np.frombuffer(s, dtype=np.uint8, count=min(hi + 3, n) - lo, offset=lo)
+    m = hi - lo
+    t = w[:m]
+    size = w[1:m + 1].astype(np.int64) | (w[2:m + 2].astype(np.int64) << 8) | (w[3:m + 3].astype(np.int64) << 16)
+    p = np.arange(lo, hi, dtype=np.int64)
+    fits = n - (p + 4) >= size
+    ok = ((t == 0xFF) & (size == 6) & (n - p >= 10)) | \
+         ((t == 1) & (size >= 4) & (size <= B + 4) & fits) | \
+         ((t == 0) & (size >= 5) & (size <= 76496 + 4) & fits)
+    return p[ok]
+
+
 def candidates(s: bytes, k: int, span: int, window: int):
-    """k_fd_candidates: span k's kept candidates (stream-relative) and their chains."""
+    """k_fd_candidates: span k's kept candidates (stream-relative) and their chains.  The scalar plausible_start runs only where
+    shape_prefilter lets a position through."""
     n = len(s)
     s0 = k * span
     s1 = min(s0 + span, n)
@@ -184,11 +203,19 @@ def candidates(s: bytes, k: int, span: int, window: int):
         starts = [0]
     else:
         starts = []
-        for p in range(s0, min(s0 + window, s1)):
+        for p in shape_prefilter(s, s0, min(s0 + window, s1)).tolist():
             if plausible_start(s, p):
                 starts.append(p)
                 if len(starts) == MAX_CAND:
                     break
+    return {p: follow_chain(s, p, s0 + span) for p in starts}
+
+
+def candidates_scalar(s: bytes, k: int, span: int, window: int):
+    """candidates() without the prefilter: plausible_start at every position of the window."""
+    s0 = k * span
+    s1 = min(s0 + span, len(s))
+    starts = [0] if k == 0 else [p for p in range(s0, min(s0 + window, s1)) if plausible_start(s, p)][:MAX_CAND]
     return {p: follow_chain(s, p, s0 + span) for p in starts}
 
 

@@ -212,3 +212,42 @@ def test_batch_plan_rows_and_both_admission_bounds(span, window):
                 assert (status[b], out_len[b]) == (O.ERR_OUTPUT_TOO_SMALL, 0)
         assert result[1] == int(out_len[status == O.OK].sum())
         assert all(c < max_chunks for c in slots)
+
+
+def _random_windows(seed: int):
+    """Random bytes with data, raw, identifier and skippable chunks (some cut short, some with a body lying about its length) at random places."""
+    rng = np.random.default_rng(seed)
+    html = read_testdata("html")
+    out = []
+    for _ in range(6):
+        s = bytearray(rng.integers(0, 256, int(rng.integers(2000, 9000)), dtype=np.uint8).tobytes())
+        for _ in range(int(rng.integers(3, 12))):
+            c = b""
+            for _ in range(int(rng.integers(1, 4))):                 # a run of chunks: its first header is a plausible start
+                o = int(rng.integers(0, len(html) - 2000))
+                piece = html[o:o + int(rng.integers(1, 1500))]
+                c += [M.data_chunk(piece), M.data_chunk(piece, compressed=False), M.STREAM_ID, M.chunk(0xFE, b"\0" * len(piece))][int(rng.integers(0, 4))]
+            if rng.integers(0, 4) == 0:
+                c = c[:int(rng.integers(1, len(c) + 1))]
+            at = int(rng.integers(0, len(s)))
+            s[at:at] = c
+        for _ in range(int(rng.integers(0, 30))):                   # loose type bytes in front of lengths that may or may not fit
+            at = int(rng.integers(0, len(s) - 4))
+            s[at] = int(rng.choice([0x00, 0x01, 0xFF]))
+        out.append(bytes(s))
+    return out
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_candidate_prefilter_equals_the_scalar_search(seed):
+    """candidates() runs plausible_start only where shape_prefilter lets a position through: the same kept candidates and chains as the scalar
+    search, on the model's hand streams and on seeded random windows; and the prefilter never drops a position chunk_shape accepts."""
+    streams = list(hand_streams().values()) + _random_windows(seed)
+    for span, window in ((256, 256), (333, 333), (1024, 200), (4096, 4096)):
+        for x in streams:
+            for k in range((len(x) + span - 1) // span):
+                assert M.candidates(x, k, span, window) == M.candidates_scalar(x, k, span, window), (span, window, k)
+    for x in streams:
+        kept = set(M.shape_prefilter(x, 0, len(x)).tolist())
+        assert {p for p in range(len(x)) if M.chunk_shape(x, p)[0]} <= kept
+        assert kept <= set(range(max(len(x) - 7, 0)))
