@@ -243,5 +243,44 @@ def frame_buffers_lib() -> C.CDLL:
     return _frame_buffers
 
 
+LAYOUT_PATH = os.path.join(HERE, "libsnappier_hip_layout.so")
+LAYOUT_HEADER_PATH = os.path.join(HERE, "..", "include", "snappier_hip_layout.h")
+_layout = None
+
+
+def layout_declared_symbols() -> list[str]:
+    """Every function name declared in include/snappier_hip_layout.h."""
+    with open(LAYOUT_HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(snp_[a-z0-9_]+)\s*\(", text)))
+
+
+def layout_lib() -> C.CDLL:
+    """libsnappier_hip_layout.so (include/snappier_hip_layout.h: device batch decoded-length query and output layout for the decode calls).  Linked
+    against the PRODUCT library, like buffers_lib()."""
+    global _layout
+    if _layout is None:
+        base = lib()
+        if os.path.realpath(base._name) != os.path.realpath(PRODUCT_PATH):
+            raise ImportError(f"libsnappier_hip_layout.so is linked against {PRODUCT_PATH}; the loaded library is {base._name}")
+        if not os.path.exists(LAYOUT_PATH):
+            raise ImportError(f"{LAYOUT_PATH} is missing: build it with `python snappier_amd/build.py`")
+        L = C.CDLL(LAYOUT_PATH)
+        missing = [s for s in layout_declared_symbols() if not hasattr(L, s)]
+        if missing:
+            raise ImportError(f"libsnappier_hip_layout.so does not export: {missing}")
+        vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
+        L.snp_decompress_layout_workspace.restype = u64
+        L.snp_decompress_layout_workspace.argtypes = [u32]
+        L.snp_decompress_layout_batch.restype = i32
+        L.snp_decompress_layout_batch.argtypes = [vp, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp, vp, vp]
+        L.snp_frame_decode_layout_workspace.restype = u64
+        L.snp_frame_decode_layout_workspace.argtypes = [u32, u32]
+        L.snp_frame_decode_layout_batch.restype = i32
+        L.snp_frame_decode_layout_batch.argtypes = [vp, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, vp, vp, vp]
+        _layout = L
+    return _layout
+
+
 def status_string(st: int) -> str:
     return lib().snp_status_string(st).decode()

@@ -133,6 +133,51 @@ class BlockCodec:
         raise_for_status(st, self.ctx.handle)
         return out_len, status, result
 
+    def decompress_layout(self, comp: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, align: int = 1, arena_cap: int = 1 << 63,
+                          work: torch.Tensor | None = None):
+        """The output layout of a block decode from the compressed bytes alone (snp_decompress_layout_batch, libsnappier_hip_layout.so):
+        -> (out_off, out_cap, declared, status, result).
+
+        out_off (int64) and out_cap (u32 in an int32 tensor) are what decompress / decompress_buffers take; declared / status are what
+        Snappy.GetUncompressedLength gives per buffer (plus the expansion rule: include/snappier_hip_layout.h).  result is the 4-element int64
+        d_result: [0] = arena bytes needed, [1] = first buffer not placed, [2] = a safe max_fragments for decompress_buffers, [3] = bytes
+        placed.  Nothing is read back; with `work` given (snp_decompress_layout_workspace bytes) the call enqueues only."""
+        self._bind()
+        nb = in_len.numel()
+        LL = N.layout_lib()
+        need = LL.snp_decompress_layout_workspace(nb)
+        if work is None:
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        if work.numel() < need:
+            raise ValueError(f"decompress_layout: work holds {work.numel()} bytes, snp_decompress_layout_workspace({nb}) = {need}")
+        if nb and comp.numel() == 0:
+            comp = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every buffer is empty: a valid pointer nothing reads)
+        out_off = torch.empty(nb, dtype=torch.int64, device=self.device)
+        out_cap = torch.empty(nb, dtype=torch.int32, device=self.device)
+        declared = torch.empty(nb, dtype=torch.int32, device=self.device)
+        status = torch.empty(nb, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        st = LL.snp_decompress_layout_batch(self.ctx.handle, _p(comp), _p(in_off), _p(in_len), nb, align, arena_cap, _p(out_off), _p(out_cap),
+                                            _p(declared), _p(status), _p(work), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return out_off, out_cap, declared, status, result
+
+    def decompress_to_memory(self, comp: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, align: int = 1, max_bytes: int | None = None):
+        """Decode a batch of blocks given nothing but the compressed tensor and its table (Snappy.DecompressToMemory over a batch):
+        -> (out, out_off, out_len, status).
+
+        decompress_layout, ONE synchronising read of its result, an output tensor of result[0] bytes (ValueError if that is above max_bytes:
+        the sizes come from the data), then decompress_buffers with max_fragments from the result.  Block b's bytes are
+        out[out_off[b] .. +out_len[b]).  status is the decoder's, except that a buffer whose preamble the layout call rejected keeps that
+        status (BAD_LENGTH, INCOMPLETE): it was given no room, so the decoder could only say OUTPUT_TOO_SMALL."""
+        out_off, out_cap, _, lstatus, result = self.decompress_layout(comp, in_off, in_len, align)
+        need, _, frags, _ = result.tolist()
+        if max_bytes is not None and need > max_bytes:
+            raise ValueError(f"decompress_to_memory: the batch declares {need} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        out_len, status, _ = self.decompress_buffers(comp, in_off, in_len, out, out_off, out_cap, max_fragments=min(frags, 0xFFFFFFFF))
+        return out[:need], out_off, out_len, torch.where(lstatus != N.OK, lstatus, status)
+
     def compact(self, data: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor):
         """Concatenate the blocks (snp_concat_batch): -> (stream tensor sized to the exact total, dst_off).  Needs the
         total on the host (one sync) to size the result."""
@@ -252,6 +297,60 @@ class BlockCodec:
             max_chunks = min(int(result[0].item()), 0xFFFFFFFF)
         call(max_chunks, work)
         return out_len, status, result
+
+    def frame_decode_layout(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, align: int = 1, arena_cap: int = 1 << 63,
+                            max_spans: int | None = None, work: torch.Tensor | None = None):
+        """The output layout of a framed batch decode from the framed bytes alone (snp_frame_decode_layout_batch, libsnappier_hip_layout.so):
+        -> (out_off, out_cap, decoded_len, nchunks, status, result).
+
+        out_off / out_cap (int64) are what frame_decode_buffers takes; decoded_len / status are what snp_frame_decoded_length gives per stream,
+        nchunks the data chunks its walk lists.  result is the 5-element int64 d_result: [0] = arena bytes needed, [1] = first stream not
+        placed, [2] = span slots needed, [3] = the max_chunks the decode call wants, [4] = spans the resolver walked on the spot.
+        Default max_spans: EXACT (sum of ceil(in_len / 2^20)), ONE synchronising read-back.  A caller that passes max_spans and work
+        (snp_frame_decode_layout_workspace bytes) enqueues only."""
+        self._bind()
+        ns = in_len.numel()
+        LL = N.layout_lib()
+        if max_spans is None:
+            n = in_len.to(torch.int64)
+            max_spans = int(((n + (1 << 20) - 1) >> 20).sum().item()) if ns else 0
+        need = LL.snp_frame_decode_layout_workspace(ns, max_spans)
+        if work is None:
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        if work.numel() < need:
+            raise ValueError(f"frame_decode_layout: work holds {work.numel()} bytes, snp_frame_decode_layout_workspace({ns}, {max_spans}) = {need}")
+        if ns and framed.numel() == 0:
+            framed = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every stream is empty: a valid pointer nothing reads)
+        out_off = torch.empty(ns, dtype=torch.int64, device=self.device)
+        out_cap = torch.empty(ns, dtype=torch.int64, device=self.device)
+        decoded_len = torch.empty(ns, dtype=torch.int64, device=self.device)
+        nchunks = torch.empty(ns, dtype=torch.int32, device=self.device)
+        status = torch.empty(ns, dtype=torch.int32, device=self.device)
+        result = torch.empty(5, dtype=torch.int64, device=self.device)
+        st = LL.snp_frame_decode_layout_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, max_spans, align, arena_cap, _p(out_off),
+                                              _p(out_cap), _p(decoded_len), _p(nchunks), _p(status), _p(work), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return out_off, out_cap, decoded_len, nchunks, status, result
+
+    def frame_decode_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, align: int = 1, max_bytes: int | None = None):
+        """Decode a batch of framed streams given nothing but the framed tensor and its table: -> (out, out_off, out_len, status).
+
+        frame_decode_layout, ONE synchronising read of its result, an output tensor of result[0] bytes (ValueError if that is above max_bytes),
+        then frame_decode_buffers with max_chunks and max_spans from the result (so without the walking call frame_decode_buffers makes to find
+        max_chunks).  The layout's max_spans is bounded without a read-back by nstreams + framed bytes / 2^20; only a table whose ranges overlap
+        can need more, and then the layout is made again with result[2].  status / out_len are frame_decode's for each stream alone."""
+        ns = in_len.numel()
+        bound = min(ns + (framed.numel() >> 20), 0xFFFFFFFF)
+        out_off, out_cap, _, _, _, result = self.frame_decode_layout(framed, in_off, in_len, align, max_spans=bound)
+        need, _, spans, chunks, _ = result.tolist()
+        if spans > bound:
+            out_off, out_cap, _, _, _, result = self.frame_decode_layout(framed, in_off, in_len, align, max_spans=spans)
+            need, _, spans, chunks, _ = result.tolist()
+        if max_bytes is not None and need > max_bytes:
+            raise ValueError(f"frame_decode_to_memory: the batch declares {need} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        out_len, status, _ = self.frame_decode_buffers(framed, in_off, in_len, out, out_off, out_cap, max_chunks=min(chunks, 0xFFFFFFFF), max_spans=spans)
+        return out[:need], out_off, out_len, status
 
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()

@@ -1,7 +1,7 @@
 """Builds the gfx950 native libraries in-tree with hipcc (cross-compiles without a GPU).
 
     python snappier_amd/build.py            # libsnappier_hip.so, libsnappier_hip_buffers.so, libsnappier_hip_buffers_decompress.so,
-                                            # libsnappier_hip_frame_buffers.so (+ libsnappier_datagen.so, bench/test helper)
+                                            # libsnappier_hip_frame_buffers.so, libsnappier_hip_layout.so (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
 
@@ -24,11 +24,14 @@ LIBS = {
     "libsnappier_hip_buffers_decompress.so": ["buffers_decode.hip"],
     # include/snappier_hip_frame_buffers.h: device batch encode / decode of many framed streams -- the same kind of extension
     "libsnappier_hip_frame_buffers.so": ["frame_buffers.hip"],
+    # include/snappier_hip_layout.h: device batch decoded-length query and output layout for the decode calls -- the same kind of extension
+    "libsnappier_hip_layout.so": ["layout.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 LINK = {"libsnappier_hip_buffers.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"],
         "libsnappier_hip_buffers_decompress.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"],
-        "libsnappier_hip_frame_buffers.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"]}   # (built after libsnappier_hip.so: LIBS keeps its order)
+        "libsnappier_hip_frame_buffers.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"],
+        "libsnappier_hip_layout.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"]}   # (built after libsnappier_hip.so: LIBS keeps its order)
 
 
 def _stale(target: str, sources: list[str]) -> bool:
