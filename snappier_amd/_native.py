@@ -34,9 +34,9 @@ DECODE_AUTO, DECODE_WAVE_ONLY, DECODE_SMALL_LANES, DECODE_SMALL_TEAM4, DECODE_SM
 COMPRESS_AUTO, COMPRESS_LANES, COMPRESS_WINDOW_LDS, COMPRESS_WINDOW_GLOBAL, COMPRESS_WINDOW_DUAL = 0, 2, 3, 4, 5
 
 
-def declared_symbols() -> list[str]:
-    """Every function name declared in include/snappier_hip.h."""
-    with open(HEADER_PATH) as f:
+def declared_symbols(header: str = HEADER_PATH) -> list[str]:
+    """Every function name declared in a C header (default: include/snappier_hip.h)."""
+    with open(header) as f:
         text = f.read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(snp_[a-z0-9_]+)\s*\(", text)))
@@ -132,154 +132,106 @@ def _load(path: str) -> C.CDLL:
     return L
 
 
-BUFFERS_PATH = os.path.join(HERE, "libsnappier_hip_buffers.so")
-BUFFERS_HEADER_PATH = os.path.join(HERE, "..", "include", "snappier_hip_buffers.h")
 PRODUCT_PATH = os.path.join(HERE, "libsnappier_hip.so")
-_buffers = None
+_vp, _u32, _u64, _i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
+# The batch extension libraries: name -> (library file, header under include/, {function: (restype, argtypes)}).  Each is linked against the
+# PRODUCT library and takes its contexts, so it is available only when lib() is the product library (not a variant under SNAPPIER_HIP_LIB, nor
+# the lab build).
+_EXTENSIONS = {
+    # buffers of any length, one block each
+    "buffers": ("libsnappier_hip_buffers.so", "snappier_hip_buffers.h", {
+        "snp_compress_buffers_workspace": (_u64, [_u32, _u32]),
+        "snp_compress_buffers_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch decompress that splits large blocks across wavefronts
+    "buffers_decompress": ("libsnappier_hip_buffers_decompress.so", "snappier_hip_buffers_decompress.h", {
+        "snp_decompress_buffers_workspace": (_u64, [_u32, _u32]),
+        "snp_decompress_buffers_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch encode and decode of many framed streams
+    "frame_buffers": ("libsnappier_hip_frame_buffers.so", "snappier_hip_frame_buffers.h", {
+        "snp_frame_encode_buffers_workspace": (_u64, [_u32, _u32]),
+        "snp_frame_encode_buffers_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "snp_frame_decode_buffers_workspace": (_u64, [_u32, _u32, _u32]),
+        "snp_frame_decode_buffers_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch decoded-length query and output layout for the decode calls
+    "layout": ("libsnappier_hip_layout.so", "snappier_hip_layout.h", {
+        "snp_decompress_layout_workspace": (_u64, [_u32]),
+        "snp_decompress_layout_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "snp_frame_decode_layout_workspace": (_u64, [_u32, _u32]),
+        "snp_frame_decode_layout_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+}
+_loaded: dict[str, C.CDLL] = {}
 
 
-def buffers_declared_symbols() -> list[str]:
-    """Every function name declared in include/snappier_hip_buffers.h."""
-    with open(BUFFERS_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(snp_[a-z0-9_]+)\s*\(", text)))
+def _extension_path(name: str) -> str:
+    return os.path.join(HERE, _EXTENSIONS[name][0])
+
+
+def _extension_header(name: str) -> str:
+    return os.path.join(HERE, "..", "include", _EXTENSIONS[name][1])
+
+
+def _extension(name: str) -> C.CDLL:
+    """The extension library `name`, loaded once: the product library must be the one in use, every symbol its header declares must be exported
+    (an installed copy without include/ falls back to the signature table, as _load does), and the signatures are bound."""
+    if name not in _loaded:
+        file, _, signatures = _EXTENSIONS[name]
+        path, header = _extension_path(name), _extension_header(name)
+        base = lib()
+        if os.path.realpath(base._name) != os.path.realpath(PRODUCT_PATH):
+            raise ImportError(f"{file} is linked against {PRODUCT_PATH}; the loaded library is {base._name}")
+        if not os.path.exists(path):
+            raise ImportError(f"{path} is missing: build it with `python snappier_amd/build.py`")
+        L = C.CDLL(path)
+        missing = [s for s in declared_symbols(header) if not hasattr(L, s)] if os.path.exists(header) else []
+        if missing:
+            raise ImportError(f"{file} does not export: {missing}")
+        for fn, (res, args) in signatures.items():
+            getattr(L, fn).restype = res
+            getattr(L, fn).argtypes = args
+        _loaded[name] = L
+    return _loaded[name]
+
+
+BUFFERS_PATH = _extension_path("buffers")
+BUFFERS_DECOMPRESS_PATH = _extension_path("buffers_decompress")
+FRAME_BUFFERS_PATH = _extension_path("frame_buffers")
+LAYOUT_PATH = _extension_path("layout")
 
 
 def buffers_lib() -> C.CDLL:
-    """libsnappier_hip_buffers.so (include/snappier_hip_buffers.h: buffers of any length, one block each).  It is linked against the PRODUCT
-    library and takes its contexts, so it is available only when lib() is the product library (not a variant under SNAPPIER_HIP_LIB, nor the
-    lab build)."""
-    global _buffers
-    if _buffers is None:
-        base = lib()
-        if os.path.realpath(base._name) != os.path.realpath(PRODUCT_PATH):
-            raise ImportError(f"libsnappier_hip_buffers.so is linked against {PRODUCT_PATH}; the loaded library is {base._name}")
-        if not os.path.exists(BUFFERS_PATH):
-            raise ImportError(f"{BUFFERS_PATH} is missing: build it with `python snappier_amd/build.py`")
-        L = C.CDLL(BUFFERS_PATH)
-        missing = [s for s in buffers_declared_symbols() if not hasattr(L, s)] if os.path.exists(BUFFERS_HEADER_PATH) else []
-        if missing:
-            raise ImportError(f"libsnappier_hip_buffers.so does not export: {missing}")
-        vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
-        L.snp_compress_buffers_workspace.restype = u64
-        L.snp_compress_buffers_workspace.argtypes = [u32, u32]
-        L.snp_compress_buffers_batch.restype = i32
-        L.snp_compress_buffers_batch.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
-        _buffers = L
-    return _buffers
-
-
-BUFFERS_DECOMPRESS_PATH = os.path.join(HERE, "libsnappier_hip_buffers_decompress.so")
-BUFFERS_DECOMPRESS_HEADER_PATH = os.path.join(HERE, "..", "include", "snappier_hip_buffers_decompress.h")
-_buffers_decompress = None
-
-
-def buffers_decompress_declared_symbols() -> list[str]:
-    """Every function name declared in include/snappier_hip_buffers_decompress.h."""
-    with open(BUFFERS_DECOMPRESS_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(snp_[a-z0-9_]+)\s*\(", text)))
+    """libsnappier_hip_buffers.so (include/snappier_hip_buffers.h)."""
+    return _extension("buffers")
 
 
 def buffers_decompress_lib() -> C.CDLL:
-    """libsnappier_hip_buffers_decompress.so (include/snappier_hip_buffers_decompress.h: device batch decompress that splits large blocks across
-    wavefronts).  Linked against the PRODUCT library, like buffers_lib()."""
-    global _buffers_decompress
-    if _buffers_decompress is None:
-        base = lib()
-        if os.path.realpath(base._name) != os.path.realpath(PRODUCT_PATH):
-            raise ImportError(f"libsnappier_hip_buffers_decompress.so is linked against {PRODUCT_PATH}; the loaded library is {base._name}")
-        if not os.path.exists(BUFFERS_DECOMPRESS_PATH):
-            raise ImportError(f"{BUFFERS_DECOMPRESS_PATH} is missing: build it with `python snappier_amd/build.py`")
-        L = C.CDLL(BUFFERS_DECOMPRESS_PATH)
-        missing = [s for s in buffers_decompress_declared_symbols() if not hasattr(L, s)]
-        if missing:
-            raise ImportError(f"libsnappier_hip_buffers_decompress.so does not export: {missing}")
-        vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
-        L.snp_decompress_buffers_workspace.restype = u64
-        L.snp_decompress_buffers_workspace.argtypes = [u32, u32]
-        L.snp_decompress_buffers_batch.restype = i32
-        L.snp_decompress_buffers_batch.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
-        _buffers_decompress = L
-    return _buffers_decompress
-
-
-FRAME_BUFFERS_PATH = os.path.join(HERE, "libsnappier_hip_frame_buffers.so")
-FRAME_BUFFERS_HEADER_PATH = os.path.join(HERE, "..", "include", "snappier_hip_frame_buffers.h")
-_frame_buffers = None
-
-
-def frame_buffers_declared_symbols() -> list[str]:
-    """Every function name declared in include/snappier_hip_frame_buffers.h."""
-    with open(FRAME_BUFFERS_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(snp_[a-z0-9_]+)\s*\(", text)))
+    """libsnappier_hip_buffers_decompress.so (include/snappier_hip_buffers_decompress.h)."""
+    return _extension("buffers_decompress")
 
 
 def frame_buffers_lib() -> C.CDLL:
-    """libsnappier_hip_frame_buffers.so (include/snappier_hip_frame_buffers.h: device batch encode and decode of many framed streams).  Linked
-    against the PRODUCT library, like buffers_lib()."""
-    global _frame_buffers
-    if _frame_buffers is None:
-        base = lib()
-        if os.path.realpath(base._name) != os.path.realpath(PRODUCT_PATH):
-            raise ImportError(f"libsnappier_hip_frame_buffers.so is linked against {PRODUCT_PATH}; the loaded library is {base._name}")
-        if not os.path.exists(FRAME_BUFFERS_PATH):
-            raise ImportError(f"{FRAME_BUFFERS_PATH} is missing: build it with `python snappier_amd/build.py`")
-        L = C.CDLL(FRAME_BUFFERS_PATH)
-        missing = [s for s in frame_buffers_declared_symbols() if not hasattr(L, s)]
-        if missing:
-            raise ImportError(f"libsnappier_hip_frame_buffers.so does not export: {missing}")
-        vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
-        L.snp_frame_encode_buffers_workspace.restype = u64
-        L.snp_frame_encode_buffers_workspace.argtypes = [u32, u32]
-        L.snp_frame_encode_buffers_batch.restype = i32
-        L.snp_frame_encode_buffers_batch.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
-        L.snp_frame_decode_buffers_workspace.restype = u64
-        L.snp_frame_decode_buffers_workspace.argtypes = [u32, u32, u32]
-        L.snp_frame_decode_buffers_batch.restype = i32
-        L.snp_frame_decode_buffers_batch.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
-        _frame_buffers = L
-    return _frame_buffers
-
-
-LAYOUT_PATH = os.path.join(HERE, "libsnappier_hip_layout.so")
-LAYOUT_HEADER_PATH = os.path.join(HERE, "..", "include", "snappier_hip_layout.h")
-_layout = None
-
-
-def layout_declared_symbols() -> list[str]:
-    """Every function name declared in include/snappier_hip_layout.h."""
-    with open(LAYOUT_HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(snp_[a-z0-9_]+)\s*\(", text)))
+    """libsnappier_hip_frame_buffers.so (include/snappier_hip_frame_buffers.h)."""
+    return _extension("frame_buffers")
 
 
 def layout_lib() -> C.CDLL:
-    """libsnappier_hip_layout.so (include/snappier_hip_layout.h: device batch decoded-length query and output layout for the decode calls).  Linked
-    against the PRODUCT library, like buffers_lib()."""
-    global _layout
-    if _layout is None:
-        base = lib()
-        if os.path.realpath(base._name) != os.path.realpath(PRODUCT_PATH):
-            raise ImportError(f"libsnappier_hip_layout.so is linked against {PRODUCT_PATH}; the loaded library is {base._name}")
-        if not os.path.exists(LAYOUT_PATH):
-            raise ImportError(f"{LAYOUT_PATH} is missing: build it with `python snappier_amd/build.py`")
-        L = C.CDLL(LAYOUT_PATH)
-        missing = [s for s in layout_declared_symbols() if not hasattr(L, s)]
-        if missing:
-            raise ImportError(f"libsnappier_hip_layout.so does not export: {missing}")
-        vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
-        L.snp_decompress_layout_workspace.restype = u64
-        L.snp_decompress_layout_workspace.argtypes = [u32]
-        L.snp_decompress_layout_batch.restype = i32
-        L.snp_decompress_layout_batch.argtypes = [vp, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp, vp, vp]
-        L.snp_frame_decode_layout_workspace.restype = u64
-        L.snp_frame_decode_layout_workspace.argtypes = [u32, u32]
-        L.snp_frame_decode_layout_batch.restype = i32
-        L.snp_frame_decode_layout_batch.argtypes = [vp, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, vp, vp, vp]
-        _layout = L
-    return _layout
+    """libsnappier_hip_layout.so (include/snappier_hip_layout.h)."""
+    return _extension("layout")
+
+
+def buffers_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("buffers"))
+
+
+def buffers_decompress_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("buffers_decompress"))
+
+
+def frame_buffers_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_buffers"))
+
+
+def layout_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("layout"))
 
 
 def status_string(st: int) -> str:

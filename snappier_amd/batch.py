@@ -31,6 +31,19 @@ class BlockCodec:
         """Follow torch's current stream, so our launches are ordered with the tensors' producers and consumers."""
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _work(self, method: str, work: torch.Tensor | None, workspace, *args: int) -> torch.Tensor:
+        """The d_work of an extension call: `workspace(*args)` bytes, allocated here when the caller passed none, checked when they did."""
+        need = workspace(*args)
+        if work is None:
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        if work.numel() < need:
+            raise ValueError(f"{method}: work holds {work.numel()} bytes, {workspace.__name__}({', '.join(map(str, args))}) = {need}")
+        return work
+
+    def _readable(self, t: torch.Tensor, n: int) -> torch.Tensor:
+        """`t`, or for an empty tensor under a batch of n > 0 empty items a 16-byte stand-in: a valid pointer that nothing reads or writes."""
+        return torch.empty(16, dtype=torch.uint8, device=self.device) if n and t.numel() == 0 else t
+
     # -- layout helpers --------------------------------------------------------------------------------------
     def uniform_layout(self, nblocks: int, block: int = N.BLOCK_SIZE, last_len: int | None = None):
         off = torch.arange(nblocks, dtype=torch.int64, device=self.device) * block
@@ -80,13 +93,8 @@ class BlockCodec:
             if max_fragments is None:
                 max_fragments = int(sums[1])
         BL = N.buffers_lib()
-        need = BL.snp_compress_buffers_workspace(nb, max_fragments)
-        if work is None:
-            work = torch.empty(need, dtype=torch.uint8, device=self.device)
-        if work.numel() < need:
-            raise ValueError(f"compress_buffers: work holds {work.numel()} bytes, snp_compress_buffers_workspace({nb}, {max_fragments}) = {need}")
-        if nb and data.numel() == 0:
-            data = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every buffer is empty: a valid pointer nothing reads)
+        work = self._work("compress_buffers", work, BL.snp_compress_buffers_workspace, nb, max_fragments)
+        data = self._readable(data, nb)
         out_len = torch.empty(nb, dtype=torch.int64, device=self.device)
         status = torch.empty(nb, dtype=torch.int32, device=self.device)
         result = torch.empty(2, dtype=torch.int64, device=self.device)
@@ -120,11 +128,7 @@ class BlockCodec:
             cap = out_cap.to(torch.int64) & 0xFFFFFFFF
             max_fragments = min(int(((cap + N.BLOCK_SIZE - 1) // N.BLOCK_SIZE).sum().item()) if nb else 0, 0xFFFFFFFF)
         BL = N.buffers_decompress_lib()
-        need = BL.snp_decompress_buffers_workspace(nb, max_fragments)
-        if work is None:
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        if work.numel() < need:
-            raise ValueError(f"decompress_buffers: work holds {work.numel()} bytes, snp_decompress_buffers_workspace({nb}, {max_fragments}) = {need}")
+        work = self._work("decompress_buffers", work, BL.snp_decompress_buffers_workspace, nb, max_fragments)
         out_len = torch.empty(nb, dtype=torch.int32, device=self.device)
         status = torch.empty(nb, dtype=torch.int32, device=self.device)
         result = torch.empty(4, dtype=torch.int64, device=self.device)
@@ -145,13 +149,8 @@ class BlockCodec:
         self._bind()
         nb = in_len.numel()
         LL = N.layout_lib()
-        need = LL.snp_decompress_layout_workspace(nb)
-        if work is None:
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        if work.numel() < need:
-            raise ValueError(f"decompress_layout: work holds {work.numel()} bytes, snp_decompress_layout_workspace({nb}) = {need}")
-        if nb and comp.numel() == 0:
-            comp = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every buffer is empty: a valid pointer nothing reads)
+        work = self._work("decompress_layout", work, LL.snp_decompress_layout_workspace, nb)
+        comp = self._readable(comp, nb)
         out_off = torch.empty(nb, dtype=torch.int64, device=self.device)
         out_cap = torch.empty(nb, dtype=torch.int32, device=self.device)
         declared = torch.empty(nb, dtype=torch.int32, device=self.device)
@@ -243,13 +242,8 @@ class BlockCodec:
             if max_chunks is None:
                 max_chunks = int(sums[1])
         FL = N.frame_buffers_lib()
-        need = FL.snp_frame_encode_buffers_workspace(nb, max_chunks)
-        if work is None:
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        if work.numel() < need:
-            raise ValueError(f"frame_encode_buffers: work holds {work.numel()} bytes, snp_frame_encode_buffers_workspace({nb}, {max_chunks}) = {need}")
-        if nb and data.numel() == 0:
-            data = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every buffer is empty: a valid pointer nothing reads)
+        work = self._work("frame_encode_buffers", work, FL.snp_frame_encode_buffers_workspace, nb, max_chunks)
+        data = self._readable(data, nb)
         out_len = torch.empty(nb, dtype=torch.int64, device=self.device)
         status = torch.empty(nb, dtype=torch.int32, device=self.device)
         result = torch.empty(2, dtype=torch.int64, device=self.device)
@@ -274,20 +268,13 @@ class BlockCodec:
         if max_spans is None:
             n = in_len.to(torch.int64)
             max_spans = int(((n + (1 << 20) - 1) >> 20).sum().item()) if ns else 0
-        if ns and framed.numel() == 0:
-            framed = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every stream is empty: a valid pointer nothing reads)
-        if ns and out.numel() == 0:
-            out = torch.empty(16, dtype=torch.uint8, device=self.device)      # (nothing to write: a valid pointer)
+        framed, out = self._readable(framed, ns), self._readable(out, ns)
         out_len = torch.empty(ns, dtype=torch.int64, device=self.device)
         status = torch.empty(ns, dtype=torch.int32, device=self.device)
         result = torch.empty(4, dtype=torch.int64, device=self.device)
 
         def call(mc: int, w: torch.Tensor | None):
-            need = FL.snp_frame_decode_buffers_workspace(ns, mc, max_spans)
-            if w is None:
-                w = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-            if w.numel() < need:
-                raise ValueError(f"frame_decode_buffers: work holds {w.numel()} bytes, snp_frame_decode_buffers_workspace({ns}, {mc}, {max_spans}) = {need}")
+            w = self._work("frame_decode_buffers", w, FL.snp_frame_decode_buffers_workspace, ns, mc, max_spans)
             st = FL.snp_frame_decode_buffers_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, mc, max_spans, _p(out), _p(out_off),
                                                    _p(out_cap), _p(out_len), _p(status), _p(w), _p(result))
             raise_for_status(st, self.ctx.handle)
@@ -314,13 +301,8 @@ class BlockCodec:
         if max_spans is None:
             n = in_len.to(torch.int64)
             max_spans = int(((n + (1 << 20) - 1) >> 20).sum().item()) if ns else 0
-        need = LL.snp_frame_decode_layout_workspace(ns, max_spans)
-        if work is None:
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        if work.numel() < need:
-            raise ValueError(f"frame_decode_layout: work holds {work.numel()} bytes, snp_frame_decode_layout_workspace({ns}, {max_spans}) = {need}")
-        if ns and framed.numel() == 0:
-            framed = torch.empty(16, dtype=torch.uint8, device=self.device)   # (every stream is empty: a valid pointer nothing reads)
+        work = self._work("frame_decode_layout", work, LL.snp_frame_decode_layout_workspace, ns, max_spans)
+        framed = self._readable(framed, ns)
         out_off = torch.empty(ns, dtype=torch.int64, device=self.device)
         out_cap = torch.empty(ns, dtype=torch.int64, device=self.device)
         decoded_len = torch.empty(ns, dtype=torch.int64, device=self.device)

@@ -19,7 +19,7 @@ LIBS = {
     "libsnappier_hip.so": ["decode_chains.hip", "decompress.hip", "decompress_small.hip", "tag_index.hip", "compress_lanes.hip", "compress_win.hip", "crc32c.hip", "framing.hip", "frame_scan.hip",
                            "capi_ctx.hip", "capi_pool.hip", "capi_batch.hip", "capi_host.hip", "capi_frame.hip"],
     # include/snappier_hip_buffers.h: buffers of any length, one block each -- an extension linked against the product library (its contexts)
-    "libsnappier_hip_buffers.so": ["buffers.hip", "capi_buffers.hip"],
+    "libsnappier_hip_buffers.so": ["buffers.hip"],
     # include/snappier_hip_buffers_decompress.h: device batch decompress that splits large blocks across wavefronts -- the same kind of extension
     "libsnappier_hip_buffers_decompress.so": ["buffers_decode.hip"],
     # include/snappier_hip_frame_buffers.h: device batch encode / decode of many framed streams -- the same kind of extension
@@ -28,10 +28,8 @@ LIBS = {
     "libsnappier_hip_layout.so": ["layout.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
-LINK = {"libsnappier_hip_buffers.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"],
-        "libsnappier_hip_buffers_decompress.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"],
-        "libsnappier_hip_frame_buffers.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"],
-        "libsnappier_hip_layout.so": ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"]}   # (built after libsnappier_hip.so: LIBS keeps its order)
+# every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)
+LINK = {lib: ["-L" + HERE, "-lsnappier_hip", "-Wl,-rpath,$ORIGIN"] for lib in LIBS if lib not in ("libsnappier_hip.so", "libsnappier_datagen.so")}
 
 
 def _stale(target: str, sources: list[str]) -> bool:

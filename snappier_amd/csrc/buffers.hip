@@ -1,15 +1,21 @@
-// buffers.hip -- device side of snp_compress_buffers_batch: many inputs of ANY length, each one Snappy block
-// (SnappyCompressor.TryCompress  SnappyCompressor.cs:24-83: varint of the whole length, then one CompressFragment per 65536 bytes, back to back).
-// The fragments of all buffers are compressed in one launch of the existing compressor (capi_batch.hip, launch_compress with the varint off,
-// into a fixed-stride staging area); what is here is the plan before it and the emit after it:
+// buffers.hip -- snp_compress_buffers_batch: many device buffers of ANY length, each compressed to ONE Snappy block
+// (SnappyCompressor.TryCompress  SnappyCompressor.cs:24-83: varint of the whole length, then one CompressFragment per 65536 bytes, back to back),
+// entirely on the device.  The host-pointer snp_try_compress does the same job for one buffer with a read-back and a host prefix sum
+// (capi_host.hip, compress_spans); here the fragments of all buffers are compressed in one launch of the existing compressor (capi_batch.hip,
+// launch_compress with the varint off, into a fixed-stride staging area), and the plan before it and the emit after it are kernels:
 //   scan    exclusive prefix sums, reduce-then-scan across workgroups (scan_tiles.h, tiles of 1024 values): fragments per buffer
 //           (ceil(len / 65536)) -> each buffer's first fragment; compressed length per fragment -> each fragment's place in its block
-//   plan    one thread per fragment slot: owning buffer (binary search over the first-fragment table), input range, staging offset;
+//   plan    one thread per fragment slot: owning buffer (owner_of over the first-fragment table), input range, staging offset;
 //           slots past the batch's fragments, and the fragments of buffers that do not fit in max_fragments, become empty fragments
 //   sizes   one thread per buffer: block size, status, out_len, the varint preamble, and the batch totals of d_result
 //   emit    one 256-thread workgroup per FRAGMENT (k_gather's copy), so a 4 GiB buffer is copied by 65 536 workgroups, not by one CU
-// Nothing here allocates or synchronises: the calls are capturable like the other _batch entry points.
+// Nothing here allocates, reads back or synchronises: the call is capturable like the other _batch entry points.  Built into
+// libsnappier_hip_buffers.so (C-ABI: include/snappier_hip_buffers.h), which is linked against libsnappier_hip.so and drives its contexts
+// through the same snp_ctx members as capi_batch.hip.  DESIGN.md 4.9.
+#include "capi_internal.h"
 #include "scan_tiles.h"
+#include "work_carver.h"
+#include "../../include/snappier_hip_buffers.h"
 
 namespace {
 
@@ -25,13 +31,7 @@ __global__ __launch_bounds__(256) void k_buffers_plan(const u64* __restrict__ in
     u64 io = 0;
     u32 il = 0, owner = kNoOwner;
     if (f < first[nbuffers]) {
-        // the buffer b with first[b] <= f < first[b + 1] (first[0] = 0 <= f < first[nbuffers] holds throughout)
-        u32 lo = 0, hi = nbuffers;
-        while (hi - lo > 1) {
-            const u32 mid = lo + (hi - lo) / 2;
-            if (first[mid] <= f) lo = mid;
-            else hi = mid;
-        }
+        const u32 lo = owner_of(first, nbuffers, f);                    // first[lo] <= f < first[lo + 1]
         if (first[lo + 1] <= max_fragments) {                          // else the buffer does not fit: its slots stay empty
             const u64 k = f - first[lo];
             const u32 n = in_len[lo];
@@ -97,59 +97,81 @@ __global__ __launch_bounds__(256) void k_buffers_emit(const u32* __restrict__ fr
     block_copy(out + o, stage + static_cast<u64>(f) * stage_stride, frag_comp_len[f], threadIdx.x);
 }
 
-__global__ void k_buffers_result_empty(u64* result)
+// d_work layout (every piece 256-byte aligned).  Per buffer: first fragment (nbuffers + 1, the last = fragments needed) and the tile sums of
+// its scan; per fragment slot: input offset and length, staging offset, compressed length, status, owning buffer, the scan of the compressed
+// lengths (max_fragments + 1) and its tile sums; then the staging area, kSnpCompStride bytes per slot (the compressor's output bound, padded).
+struct BuffersWork {
+    u64 *first, *first_part, *frag_in_off, *frag_stage_off, *frag_scan, *frag_part;
+    u32 *frag_in_len, *frag_comp_len, *frag_owner;
+    i32* frag_status;
+    u8* stage;
+    u64 bytes;
+};
+BuffersWork buffers_work_layout(void* base, u32 nbuffers, u32 max_fragments)
 {
-    if (threadIdx.x < 2) result[threadIdx.x] = 0;
+    BuffersWork w{};
+    if (nbuffers == 0) return w;                                         // (nothing is launched but the result)
+    const u64 nb = nbuffers, nf = max_fragments;
+    WorkCarver k(base);
+    w.first = k.take<u64>(nb + 1);
+    w.first_part = k.take<u64>(scan_tiles_of(nb));
+    w.frag_scan = k.take<u64>(nf + 1);
+    w.frag_part = k.take<u64>(scan_tiles_of(nf));
+    w.frag_in_off = k.take<u64>(nf);
+    w.frag_stage_off = k.take<u64>(nf);
+    w.frag_in_len = k.take<u32>(nf);
+    w.frag_comp_len = k.take<u32>(nf);
+    w.frag_owner = k.take<u32>(nf);
+    w.frag_status = k.take<i32>(nf);
+    w.stage = k.take<u8>(nf * kSnpCompStride);
+    w.bytes = k.bytes();
+    return w;
 }
 
 }  // namespace
 
 extern "C" {
 
-// first[0 .. nbuffers] = exclusive scan of ceil(in_len / 65536); result = {fragments needed, 0}
-hipError_t snp_launch_buffers_first(const u32* in_len, u32 nbuffers, u64* partial, u64* first, u64* result, hipStream_t stream)
+uint64_t snp_compress_buffers_workspace(uint32_t nbuffers, uint32_t max_fragments)
 {
-    return launch_scan(ScanFrags{in_len}, nbuffers, partial, first, result, stream);
+    return buffers_work_layout(nullptr, nbuffers, max_fragments).bytes;
 }
 
-hipError_t snp_launch_buffers_plan(const u64* in_off, const u32* in_len, u32 nbuffers, const u64* first, u32 max_fragments, u64 stage_stride,
-                                   u64* frag_in_off, u32* frag_in_len, u64* frag_stage_off, u32* frag_owner, hipStream_t stream)
+snp_status snp_compress_buffers_batch(snp_ctx* c, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t nbuffers,
+                                      uint32_t max_fragments, uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap,
+                                      uint64_t* out_len, int32_t* status, void* d_work, uint64_t* d_result)
 {
-    if (max_fragments == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_buffers_plan, dim3((max_fragments + 255u) / 256u), dim3(256), 0, stream, in_off, in_len, nbuffers, first, max_fragments,
-                       stage_stride, frag_in_off, frag_in_len, frag_stage_off, frag_owner);
-    return hipGetLastError();
-}
-
-// frag_scan[0 .. nfrag] = exclusive scan of the compressed lengths
-hipError_t snp_launch_buffers_frag_scan(const u32* comp_len, u32 nfrag, u64* partial, u64* frag_scan, hipStream_t stream)
-{
-    return launch_scan(ScanPlain{comp_len}, nfrag, partial, frag_scan, nullptr, stream);
-}
-
-hipError_t snp_launch_buffers_sizes(const u32* in_len, u32 nbuffers, const u64* first, u32 max_fragments, const u64* frag_scan, u8* out,
-                                    const u64* out_off, const u64* out_cap, u64* out_len, i32* status, u64* result, hipStream_t stream)
-{
-    if (nbuffers == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_buffers_sizes, dim3((nbuffers + 255u) / 256u), dim3(256), 0, stream, in_len, nbuffers, first, max_fragments, frag_scan,
-                       out, out_off, out_cap, out_len, status, result);
-    return hipGetLastError();
-}
-
-hipError_t snp_launch_buffers_emit(const u32* frag_owner, const u32* frag_comp_len, const u64* frag_scan, const u64* first, const u32* in_len,
-                                   const i32* status, const u8* stage, u64 stage_stride, u8* out, const u64* out_off, u32 max_fragments,
-                                   hipStream_t stream)
-{
-    if (max_fragments == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_buffers_emit, dim3(max_fragments), dim3(256), 0, stream, frag_owner, frag_comp_len, frag_scan, first, in_len, status,
-                       stage, stage_stride, out, out_off);
-    return hipGetLastError();
-}
-
-hipError_t snp_launch_buffers_result_empty(u64* result, hipStream_t stream)
-{
-    hipLaunchKernelGGL(k_buffers_result_empty, dim3(1), dim3(64), 0, stream, result);
-    return hipGetLastError();
+    if (!c || !d_result || (nbuffers && (!in || !in_off || !in_len || !out || !out_off || !out_cap || !out_len || !status || !d_work)))
+        return SNP_ERR_BAD_ARG;
+    DevGuard dg(c);
+    if (!dg.ok) return SNP_ERR_DEVICE;
+    hipStream_t s = c->stream;
+    if (nbuffers == 0)
+        return c->check(snp_zero_words_async(reinterpret_cast<u32*>(d_result), 2 * 2u, s), "buffers result") ? SNP_OK : SNP_ERR_DEVICE;   // 2 u64 words
+    const BuffersWork w = buffers_work_layout(d_work, nbuffers, max_fragments);
+    const u32 nb = nbuffers, M = max_fragments;
+    // plan: first fragment of every buffer (d_result = {fragments needed, 0}), then the fragment table over all max_fragments slots
+    bool ok = c->check(launch_scan(ScanFrags{in_len}, nb, w.first_part, w.first, d_result, s), "buffers scan");
+    if (ok && M) {
+        hipLaunchKernelGGL(k_buffers_plan, dim3((M + 255u) / 256u), dim3(256), 0, s, in_off, in_len, nb, w.first, M, kSnpCompStride, w.frag_in_off,
+                           w.frag_in_len, w.frag_stage_off, w.frag_owner);
+        // compress: every slot, the empty ones included (the count picks the layout: DESIGN.md 4.9), no varint -- CompressFragment only
+        ok = c->check(hipGetLastError(), "buffers plan") &&
+             c->launch_compress(in, w.frag_in_off, w.frag_in_len, M, w.stage, w.frag_stage_off, w.frag_comp_len, w.frag_status, 0);
+    }
+    // the scan of the compressed lengths, the sizes, then the fragments to their places (a buffer that is not OK is not written at all)
+    ok = ok && c->check(launch_scan(ScanPlain{w.frag_comp_len}, M, w.frag_part, w.frag_scan, nullptr, s), "fragment scan");
+    if (ok) {
+        hipLaunchKernelGGL(k_buffers_sizes, dim3((nb + 255u) / 256u), dim3(256), 0, s, in_len, nb, w.first, M, w.frag_scan, out, out_off, out_cap,
+                           out_len, status, d_result);
+        ok = c->check(hipGetLastError(), "buffers sizes");
+    }
+    if (ok && M) {
+        hipLaunchKernelGGL(k_buffers_emit, dim3(M), dim3(256), 0, s, w.frag_owner, w.frag_comp_len, w.frag_scan, w.first, in_len, status, w.stage,
+                           kSnpCompStride, out, out_off);
+        ok = c->check(hipGetLastError(), "buffers emit");
+    }
+    return ok ? SNP_OK : SNP_ERR_DEVICE;
 }
 
 }  // extern "C"

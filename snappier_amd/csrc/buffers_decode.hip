@@ -15,6 +15,7 @@
 #include "capi_internal.h"
 #include "scan_tiles.h"
 #include "tag_index_device.h"
+#include "work_carver.h"
 #include "../../include/snappier_hip_buffers_decompress.h"
 
 namespace {
@@ -38,19 +39,6 @@ __device__ __forceinline__ bool admitted(const u64* __restrict__ first, u32 b, u
 }
 // packed[b] = (chunks before b) << 32 | (split blocks before b); a split block's tag-index slots start at chunks + 2 * blocks
 __device__ __forceinline__ u64 slot_of(const u64* __restrict__ packed, u32 b) { return (packed[b] >> 32) + 2ull * static_cast<u32>(packed[b]); }
-
-// the last b in [0, nb) with key(b) <= t (key non-decreasing, key(0) = 0)
-template <class K>
-__device__ __forceinline__ u32 find_block(K key, u32 nb, u64 t)
-{
-    u32 lo = 0, hi = nb;
-    while (hi - lo > 1) {
-        const u32 mid = lo + (hi - lo) / 2;
-        if (key(mid) <= t) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // ---- classify + plan -------------------------------------------------------------------------------------------------------------------------
 // decl[b] = declared length of a candidate, else 0; hbv[b] = preamble bytes.  Workgroup 0 also zeroes the global words and d_result[2..3].
@@ -179,7 +167,7 @@ __global__ __launch_bounds__(kThreads) void k_bd_tag_cand(const u8* __restrict__
         if (threadIdx.x == 0) {
             const u32 tk = atomicAdd(&glob[0], 1u);
             s_ticket = tk;
-            s_b = tk < total ? find_block([=](u32 b) { return packed[b] >> 32; }, nb, tk) : 0u;
+            s_b = tk < total ? owner_of([=](u32 b) { return packed[b] >> 32; }, nb, tk) : 0u;
         }
         __syncthreads();
         const u32 tk = s_ticket;
@@ -281,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void k_bd_tag_scan(const u8* __restrict__
         if (threadIdx.x == 0) {
             const u32 tk = atomicAdd(&glob[2], 1u);
             s_ticket = tk;
-            s_b = tk < nsplit ? find_block([=](u32 b) { return static_cast<u64>(static_cast<u32>(packed[b])); }, nb, tk) : 0u;
+            s_b = tk < nsplit ? owner_of([=](u32 b) { return static_cast<u64>(static_cast<u32>(packed[b])); }, nb, tk) : 0u;
         }
         __syncthreads();
         if (s_ticket >= nsplit) return;
@@ -318,7 +306,7 @@ __global__ __launch_bounds__(kThreads) void k_bd_tag_look_back(const u8* __restr
         if (threadIdx.x == 0) {
             const u32 tk = atomicAdd(&glob[1], 1u);
             s_ticket = tk;
-            s_b = tk < total ? find_block([=](u32 b) { return packed[b] >> 32; }, nb, tk) : 0u;
+            s_b = tk < total ? owner_of([=](u32 b) { return packed[b] >> 32; }, nb, tk) : 0u;
         }
         __syncthreads();
         const u32 tk = s_ticket;
@@ -372,7 +360,7 @@ __global__ __launch_bounds__(256) void k_bd_fragment_starts(const u64* __restric
     u64 io = 0, oo = 0;
     u32 il = 0, cap = 0, skip = 0, owner = kNone;
     if (f < first[nb]) {
-        const u32 b = find_block([=](u32 i) { return first[i]; }, nb, f);
+        const u32 b = owner_of(first, nb, f);
         if (first[b + 1] <= max_fragments) {
             const u32 n = in_len[b], expected = decl[b];
             const u64 slot = slot_of(packed, b);
@@ -450,11 +438,6 @@ __global__ __launch_bounds__(256) void k_bd_finalize(u32 nb, const u64* __restri
     }
 }
 
-__global__ void k_bd_result_empty(u64* result)
-{
-    if (threadIdx.x < 4) result[threadIdx.x] = 0;
-}
-
 // d_work layout (every piece 256-byte aligned; nothing when nbuffers is 0).  Per block: the classification, the masked lengths, the fallback list,
 // the control words and three scans over nbuffers + 1 values with their tile sums; the global control words; per fragment slot: the fragment
 // table; per tag-index slot (kSlotsPerFragment per fragment): scanned and looked-back entries (kSubs each), a hand-off, a candidate table; then
@@ -479,34 +462,32 @@ DecodeWork decode_work_layout(void* base, u32 nbuffers, u32 max_fragments)
     const u64 nb = nbuffers, nf = max_fragments < kMaxFragments ? max_fragments : kMaxFragments, ns = nf * kSlotsPerFragment;
     w.max_fragments = static_cast<u32>(nf);
     w.scan_wgs = static_cast<u32>(nf < kScanSlots ? nf : kScanSlots);
-    u8* p = static_cast<u8*>(base);
-    u64 o = 0;
-    auto take = [&](u64 bytes) { u8* r = p ? p + o : nullptr; o += snp_align_up(bytes, 256); return r; };
-    w.decl = reinterpret_cast<u32*>(take(nb * 4));
-    w.hbv = reinterpret_cast<u32*>(take(nb * 4));
-    w.m_in_len = reinterpret_cast<u32*>(take(nb * 4));
-    w.m_out_cap = reinterpret_cast<u32*>(take(nb * 4));
-    w.list = reinterpret_cast<u32*>(take(nb * 4));
-    w.ctl = reinterpret_cast<u32*>(take(nb * kCtlWords * 4));
-    w.sum = reinterpret_cast<u64*>(take((nb + 1) * 8));
-    w.first = reinterpret_cast<u64*>(take((nb + 1) * 8));
-    w.packed = reinterpret_cast<u64*>(take((nb + 1) * 8));
-    w.part = reinterpret_cast<u64*>(take(((nb + SNP_SCAN_TILE - 1) / SNP_SCAN_TILE + 1) * 8));
-    w.glob = reinterpret_cast<u32*>(take(kGlobWords * 4));
-    w.f_in_off = reinterpret_cast<u64*>(take(nf * 8));
-    w.f_out_off = reinterpret_cast<u64*>(take(nf * 8));
-    w.f_in_len = reinterpret_cast<u32*>(take(nf * 4));
-    w.f_out_cap = reinterpret_cast<u32*>(take(nf * 4));
-    w.f_skip = reinterpret_cast<u32*>(take(nf * 4));
-    w.f_out_len = reinterpret_cast<u32*>(take(nf * 4));
-    w.f_owner = reinterpret_cast<u32*>(take(nf * 4));
-    w.f_status = reinterpret_cast<i32*>(take(nf * 4));
-    w.scanned = reinterpret_cast<u64*>(take(ns * kSubs * 8));
-    w.looked = reinterpret_cast<u64*>(take(ns * kSubs * 8));
-    w.hand = reinterpret_cast<CandHandoff*>(take(ns * sizeof(CandHandoff)));
-    w.tables = reinterpret_cast<CandTable*>(take(ns * sizeof(CandTable)));
-    w.caches = reinterpret_cast<RunCache*>(take(static_cast<u64>(w.scan_wgs) * sizeof(RunCache)));
-    w.bytes = o;
+    WorkCarver k(base);
+    w.decl = k.take<u32>(nb);
+    w.hbv = k.take<u32>(nb);
+    w.m_in_len = k.take<u32>(nb);
+    w.m_out_cap = k.take<u32>(nb);
+    w.list = k.take<u32>(nb);
+    w.ctl = k.take<u32>(nb * kCtlWords);
+    w.sum = k.take<u64>(nb + 1);
+    w.first = k.take<u64>(nb + 1);
+    w.packed = k.take<u64>(nb + 1);
+    w.part = k.take<u64>(scan_tiles_of(nb));
+    w.glob = k.take<u32>(kGlobWords);
+    w.f_in_off = k.take<u64>(nf);
+    w.f_out_off = k.take<u64>(nf);
+    w.f_in_len = k.take<u32>(nf);
+    w.f_out_cap = k.take<u32>(nf);
+    w.f_skip = k.take<u32>(nf);
+    w.f_out_len = k.take<u32>(nf);
+    w.f_owner = k.take<u32>(nf);
+    w.f_status = k.take<i32>(nf);
+    w.scanned = k.take<u64>(ns * kSubs);
+    w.looked = k.take<u64>(ns * kSubs);
+    w.hand = k.take<CandHandoff>(ns);
+    w.tables = k.take<CandTable>(ns);
+    w.caches = k.take<RunCache>(w.scan_wgs);
+    w.bytes = k.bytes();
     return w;
 }
 
@@ -528,10 +509,8 @@ snp_status snp_decompress_buffers_batch(snp_ctx* c, const uint8_t* in, const uin
     DevGuard dg(c);
     if (!dg.ok) return SNP_ERR_DEVICE;
     hipStream_t s = c->stream;
-    if (nbuffers == 0) {
-        hipLaunchKernelGGL(k_bd_result_empty, dim3(1), dim3(64), 0, s, d_result);
-        return c->check(hipGetLastError(), "buffers result") ? SNP_OK : SNP_ERR_DEVICE;
-    }
+    if (nbuffers == 0)
+        return c->check(snp_zero_words_async(reinterpret_cast<u32*>(d_result), 2 * 4u, s), "buffers result") ? SNP_OK : SNP_ERR_DEVICE;   // 4 u64 words
     const DecodeWork w = decode_work_layout(d_work, nbuffers, max_fragments);
     const u32 nb = nbuffers, M = w.max_fragments, grid_b = (nb + 255u) / 256u;
     const int dec_mode = c->fenced | ((c->dec_lds / 256) << 8);

@@ -5,11 +5,11 @@
 //     capi_batch.hip   launch policy of the device-pointer batch entry points (which kernel for which batch), snp_*_batch
 //     capi_host.hip    the host-pointer calls: snp_try_compress / snp_try_decompress (+ segments), snp_crc32c
 //     capi_frame.hip   framing orchestration: snp_frame_encode* / snp_frame_decode*
-//     capi_buffers.hip snp_compress_buffers_batch: buffers of any length, one block each (plan / scan / emit kernels in buffers.hip) -- these two
-//                      form libsnappier_hip_buffers.so (include/snappier_hip_buffers.h), linked against libsnappier_hip.so; buffers_decode.hip and
-//                      frame_buffers.hip form two more such extensions (snappier_hip_buffers_decompress.h, snappier_hip_frame_buffers.h)
+// The batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip: one file and one header under include/ each)
+// are linked against libsnappier_hip.so and drive its contexts through this header; what they share among themselves is in work_carver.h,
+// scan_tiles.h and frame_walk_device.h.
 // No codec arithmetic happens on the host: every byte of compress / decompress / CRC work is done by the gfx950 kernels in compress_lanes.hip,
-// compress_win.hip, decode_chains.hip, decompress.hip, decompress_small.hip, tag_index.hip, crc32c.hip, framing.hip, frame_scan.hip, buffers.hip.
+// compress_win.hip, decode_chains.hip, decompress.hip, decompress_small.hip, tag_index.hip, crc32c.hip, framing.hip, frame_scan.hip.
 // There is no CPU fallback -- without a HIP device snp_ctx_create fails with SNP_ERR_DEVICE.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,13 +64,6 @@ size_t snp_frame_scan_workspace(u64);
 hipError_t snp_launch_frame_scan_spans(const u8*, u64, u64, u32, u8*, u64*, u32*, u32*, u64*, u32*, u64*, void*, hipStream_t);
 hipError_t snp_launch_frame_emit(const u8*, const u64*, const u8*, const u64*, const u8*, const u32*, const u32*,
                                  const u64*, u8*, u64, u32, hipStream_t);
-hipError_t snp_launch_buffers_first(const u32*, u32, u64*, u64*, u64*, hipStream_t);
-hipError_t snp_launch_buffers_plan(const u64*, const u32*, u32, const u64*, u32, u64, u64*, u32*, u64*, u32*, hipStream_t);
-hipError_t snp_launch_buffers_frag_scan(const u32*, u32, u64*, u64*, hipStream_t);
-hipError_t snp_launch_buffers_sizes(const u32*, u32, const u64*, u32, const u64*, u8*, const u64*, const u64*, u64*, i32*, u64*, hipStream_t);
-hipError_t snp_launch_buffers_emit(const u32*, const u32*, const u64*, const u64*, const u32*, const i32*, const u8*, u64, u8*, const u64*, u32,
-                                   hipStream_t);
-hipError_t snp_launch_buffers_result_empty(u64*, hipStream_t);
 }
 
 constexpr u64 kSnpCompStride = 76496 + 16;   // snp_max_compressed_length(65536), padded to a 16-byte multiple

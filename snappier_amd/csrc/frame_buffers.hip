@@ -223,14 +223,7 @@ __global__ __launch_bounds__(256) void k_fd_verdict(u32 ns, const u64* __restric
     if ((threadIdx.x & 63u) == 0 && ok_len) atomicAdd(reinterpret_cast<unsigned long long*>(result + 1), static_cast<unsigned long long>(ok_len));
 }
 
-__global__ void k_fb_result_empty(u64* result, u32 n)
-{
-    if (threadIdx.x < n) result[threadIdx.x] = 0;
-}
-
 // ---- workspaces (every piece 256-byte aligned; nothing when there is no buffer) --------------------------------------------------------------
-inline u64 scan_tiles_of(u64 n) { return (n + SNP_SCAN_TILE - 1) / SNP_SCAN_TILE + 1; }
-
 // encode.  Per buffer: first chunk slot (nb + 1) and its tile sums.  Per slot: input offset and length, staging offset, compressed length,
 // compressor status, owner, masked CRC, the scan of the framed sizes (max_chunks + 1) and its tile sums; then kSnpCompStride of staging.
 struct EncodeWork {
@@ -245,22 +238,20 @@ EncodeWork encode_work_layout(void* base, u32 nbuffers, u32 max_chunks)
     EncodeWork w{};
     if (nbuffers == 0) return w;
     const u64 nb = nbuffers, nc = max_chunks;
-    u8* p = static_cast<u8*>(base);
-    u64 o = 0;
-    auto take = [&](u64 bytes) { u8* r = p ? p + o : nullptr; o += snp_align_up(bytes, 256); return r; };
-    w.first = reinterpret_cast<u64*>(take((nb + 1) * 8));
-    w.first_part = reinterpret_cast<u64*>(take(scan_tiles_of(nb) * 8));
-    w.cscan = reinterpret_cast<u64*>(take((nc + 1) * 8));
-    w.c_part = reinterpret_cast<u64*>(take(scan_tiles_of(nc) * 8));
-    w.c_in_off = reinterpret_cast<u64*>(take(nc * 8));
-    w.c_stage_off = reinterpret_cast<u64*>(take(nc * 8));
-    w.c_in_len = reinterpret_cast<u32*>(take(nc * 4));
-    w.comp_len = reinterpret_cast<u32*>(take(nc * 4));
-    w.c_owner = reinterpret_cast<u32*>(take(nc * 4));
-    w.crc = reinterpret_cast<u32*>(take(nc * 4));
-    w.c_status = reinterpret_cast<i32*>(take(nc * 4));
-    w.stage = take(nc * kSnpCompStride);
-    w.bytes = o;
+    WorkCarver k(base);
+    w.first = k.take<u64>(nb + 1);
+    w.first_part = k.take<u64>(scan_tiles_of(nb));
+    w.cscan = k.take<u64>(nc + 1);
+    w.c_part = k.take<u64>(scan_tiles_of(nc));
+    w.c_in_off = k.take<u64>(nc);
+    w.c_stage_off = k.take<u64>(nc);
+    w.c_in_len = k.take<u32>(nc);
+    w.comp_len = k.take<u32>(nc);
+    w.c_owner = k.take<u32>(nc);
+    w.crc = k.take<u32>(nc);
+    w.c_status = k.take<i32>(nc);
+    w.stage = k.take<u8>(nc * kSnpCompStride);
+    w.bytes = k.bytes();
     return w;
 }
 
@@ -278,42 +269,27 @@ DecodeWork decode_work_layout(void* base, u32 nstreams, u32 max_chunks, u32 max_
     DecodeWork w{};
     if (nstreams == 0) return w;
     const u64 ns = nstreams, nc = max_chunks, nsp = max_spans;
-    u8* p = static_cast<u8*>(base);
-    u64 o = 0;
-    auto take = [&](u64 bytes) { u8* r = p ? p + o : nullptr; o += snp_align_up(bytes, 256); return r; };
-    w.sfirst = reinterpret_cast<u64*>(take((ns + 1) * 8));
-    w.cfirst = reinterpret_cast<u64*>(take((ns + 1) * 8));
-    w.part = reinterpret_cast<u64*>(take(scan_tiles_of(ns) * 8));
-    w.st.total = reinterpret_cast<u64*>(take(ns * 8));
-    w.st.tail = reinterpret_cast<i32*>(take(ns * 4));
-    w.st.nc = reinterpret_cast<u32*>(take(ns * 4));
-    w.st.fail = reinterpret_cast<u32*>(take(ns * 4));
-    w.sp.count = reinterpret_cast<u32*>(take(nsp * 4));
-    w.sp.start_rel = reinterpret_cast<u32*>(take(nsp * kMaxCand * 4));
-    w.sp.exit = reinterpret_cast<u64*>(take(nsp * kMaxCand * 8));
-    w.sp.dec = reinterpret_cast<u64*>(take(nsp * kMaxCand * 8));
-    w.sp.ndata = reinterpret_cast<u32*>(take(nsp * kMaxCand * 4));
-    w.sp.stop = reinterpret_cast<i32*>(take(nsp * kMaxCand * 4));
-    w.sp.entry = reinterpret_cast<u64*>(take(nsp * 8));
-    w.sp.chunk_base = reinterpret_cast<u32*>(take(nsp * 4));
-    w.sp.out_base = reinterpret_cast<u64*>(take(nsp * 8));
-    w.r.body_off = reinterpret_cast<u64*>(take(nc * 8));
-    w.r.out_off = reinterpret_cast<u64*>(take(nc * 8));
-    w.r.body_len = reinterpret_cast<u32*>(take(nc * 4));
-    w.r.crc = reinterpret_cast<u32*>(take(nc * 4));
-    w.r.out_cap = reinterpret_cast<u32*>(take(nc * 4));
-    w.r.out_len = reinterpret_cast<u32*>(take(nc * 4));
-    w.r.owner = reinterpret_cast<u32*>(take(nc * 4));
-    w.r.status = reinterpret_cast<i32*>(take(nc * 4));
-    w.r.type = take(nc);
-    w.bytes = o;
+    WorkCarver k(base);
+    w.sfirst = k.take<u64>(ns + 1);
+    w.cfirst = k.take<u64>(ns + 1);
+    w.part = k.take<u64>(scan_tiles_of(ns));
+    carve_span_walk(k, ns, nsp, w.st, w.sp);
+    w.r.body_off = k.take<u64>(nc);
+    w.r.out_off = k.take<u64>(nc);
+    w.r.body_len = k.take<u32>(nc);
+    w.r.crc = k.take<u32>(nc);
+    w.r.out_cap = k.take<u32>(nc);
+    w.r.out_len = k.take<u32>(nc);
+    w.r.owner = k.take<u32>(nc);
+    w.r.status = k.take<i32>(nc);
+    w.r.type = k.take<u8>(nc);
+    w.bytes = k.bytes();
     return w;
 }
 
-bool result_empty(snp_ctx* c, u64* d_result, u32 n)
+bool result_empty(snp_ctx* c, u64* d_result, u32 words)
 {
-    hipLaunchKernelGGL(k_fb_result_empty, dim3(1), dim3(64), 0, c->stream, d_result, n);
-    return c->check(hipGetLastError(), "frame buffers result");
+    return c->check(snp_zero_words_async(reinterpret_cast<u32*>(d_result), 2 * words, c->stream), "frame buffers result");
 }
 
 }  // namespace
@@ -378,12 +354,8 @@ snp_status snp_frame_decode_buffers_batch(snp_ctx* c, const uint8_t* in, const u
     const DecodeWork w = decode_work_layout(d_work, nstreams, max_chunks, max_spans);
     const u32 ns = nstreams, M = max_chunks, S = max_spans;
     // the span walk: first span slot of every stream (d_result[2] = span slots needed, d_result[3] = 0), candidates, one chain per stream
-    bool ok = c->check(launch_scan(ScanPieces{in_len, kSpan}, ns, w.part, w.sfirst, d_result + 2, s), "frame buffers span scan");
-    if (ok) {
-        if (S) hipLaunchKernelGGL(k_fd_candidates, dim3(S), dim3(SNP_WAVE), 0, s, in, in_off, in_len, ns, w.sfirst, S, w.sp);
-        hipLaunchKernelGGL(k_fd_resolve, dim3(ns), dim3(SNP_WAVE), 0, s, in, in_off, in_len, out_cap, w.sfirst, S, w.sp, w.st, d_result + 3);
-        ok = c->check(hipGetLastError(), "frame buffers walk");
-    }
+    bool ok = c->check(launch_span_scan(in_len, ns, w.part, w.sfirst, d_result + 2, s), "frame buffers span scan") &&
+              c->check(launch_span_walk(in, in_off, in_len, out_cap, ns, w.sfirst, S, w.sp, w.st, d_result + 3, s), "frame buffers walk");
     // first chunk slot of every stream (d_result[0] = chunk slots needed, d_result[1] = 0), then the chunk table over all max_chunks slots
     ok = ok && c->check(launch_scan(ScanPlain{w.st.nc}, ns, w.part, w.cfirst, d_result, s), "frame buffers chunk scan");
     if (ok && M) {

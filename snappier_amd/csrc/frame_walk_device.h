@@ -1,28 +1,18 @@
-// frame_walk_device.h -- the span walk over MANY framed streams: the span tables, the per-stream record, walk A (k_fd_candidates) and walk B
-// (k_fd_resolve) that the batch decode (frame_buffers.hip, snp_frame_decode_buffers_batch) and the decode layout (layout.hip,
-// snp_frame_decode_layout_batch) share, with the piece scan that gives every stream its first span slot.  Moved here from frame_buffers.hip;
-// the one change is that the resolver takes out_cap == nullptr as "no bound" (the layout call asks for the totals, it has no capacities yet).
+// frame_walk_device.h -- the span walk over MANY framed streams, end to end: the span tables and the per-stream record with their place in a
+// workspace (carve_span_walk), the piece scan that gives every stream its first span slot (launch_span_scan), walk A (k_fd_candidates) and walk B
+// (k_fd_resolve) with their launch (launch_span_walk).  Shared by the batch decode (frame_buffers.hip, snp_frame_decode_buffers_batch) and the
+// decode layout (layout.hip, snp_frame_decode_layout_batch); the resolver takes out_cap == nullptr as "no bound" (the layout call asks for the
+// totals, it has no capacities yet).
 #pragma once
 #include "scan_tiles.h"
 #include "frame_hop_device.h"
+#include "work_carver.h"
 
 namespace {
 
 constexpr u32 kNone = 0xffffffffu;
 
 __host__ __device__ __forceinline__ u64 ceil_div(u64 n, u64 d) { return n / d + (n % d != 0); }
-
-// the last b in [0, nb) with first[b] <= t (first non-decreasing, first[0] = 0): the owner of slot t < first[nb]
-__device__ __forceinline__ u32 owner_of(const u64* __restrict__ first, u32 nb, u64 t)
-{
-    u32 lo = 0, hi = nb;
-    while (hi - lo > 1) {
-        const u32 mid = lo + (hi - lo) / 2;
-        if (first[mid] <= t) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // scan source: pieces of `unit` bytes in a u64 length (chunks, spans)
 struct ScanPieces {
@@ -180,6 +170,42 @@ __global__ __launch_bounds__(SNP_WAVE) void k_fd_resolve(const u8* __restrict__ 
         st.fail[b] = kNone;
         if (missed) atomicAdd(reinterpret_cast<unsigned long long*>(missed_total), static_cast<unsigned long long>(missed));
     }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------------
+// The walk's pieces of a workspace, in the order both callers have always had them: the per-stream record, then per span slot the candidates
+// and the resolver's entry.  (Each caller carves sfirst, its second per-stream table and the tile sums before this.)
+inline void carve_span_walk(WorkCarver& k, u64 ns, u64 max_spans, FbStreams& st, FbSpans& sp)
+{
+    st.total = k.take<u64>(ns);
+    st.tail = k.take<i32>(ns);
+    st.nc = k.take<u32>(ns);
+    st.fail = k.take<u32>(ns);
+    sp.count = k.take<u32>(max_spans);
+    sp.start_rel = k.take<u32>(max_spans * kMaxCand);
+    sp.exit = k.take<u64>(max_spans * kMaxCand);
+    sp.dec = k.take<u64>(max_spans * kMaxCand);
+    sp.ndata = k.take<u32>(max_spans * kMaxCand);
+    sp.stop = k.take<i32>(max_spans * kMaxCand);
+    sp.entry = k.take<u64>(max_spans);
+    sp.chunk_base = k.take<u32>(max_spans);
+    sp.out_base = k.take<u64>(max_spans);
+}
+
+// sfirst[0 .. ns] = first span slot of every stream; span_result[0] = span slots needed, span_result[1] = 0.  The word launch_span_walk adds
+// to must be zero by then: the scan does that when the word follows the count, a caller that keeps it elsewhere clears it between the two.
+inline hipError_t launch_span_scan(const u64* in_len, u32 ns, u64* part, u64* sfirst, u64* span_result, hipStream_t stream)
+{
+    return launch_scan(ScanPieces{in_len, kSpan}, ns, part, sfirst, span_result, stream);
+}
+
+// walks A and B over max_spans slots; out_cap == nullptr: no bound; *missed += spans the resolver walked on the spot
+inline hipError_t launch_span_walk(const u8* in, const u64* in_off, const u64* in_len, const u64* out_cap, u32 ns, const u64* sfirst,
+                                   u32 max_spans, const FbSpans& sp, const FbStreams& st, u64* missed, hipStream_t stream)
+{
+    if (max_spans) hipLaunchKernelGGL(k_fd_candidates, dim3(max_spans), dim3(SNP_WAVE), 0, stream, in, in_off, in_len, ns, sfirst, max_spans, sp);
+    hipLaunchKernelGGL(k_fd_resolve, dim3(ns), dim3(SNP_WAVE), 0, stream, in, in_off, in_len, out_cap, sfirst, max_spans, sp, st, missed);
+    return hipGetLastError();
 }
 
 }  // namespace

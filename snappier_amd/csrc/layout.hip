@@ -213,8 +213,6 @@ __global__ __launch_bounds__(256) void k_fl_write(u32 ns, const u64* __restrict_
 }
 
 // ---- workspaces (every piece 256-byte aligned; nothing when there is no item) ------------------------------------------------------------------
-inline u64 scan_tiles_of(u64 n) { return (n + SNP_SCAN_TILE - 1) / SNP_SCAN_TILE + 1; }
-
 // blocks: each buffer's offset (nb + 1) and the tile sums of its scan
 struct BlockWork {
     u64 *off, *part;
@@ -225,12 +223,10 @@ BlockWork block_work_layout(void* base, u32 nbuffers)
     BlockWork w{};
     if (nbuffers == 0) return w;
     const u64 nb = nbuffers;
-    u8* p = static_cast<u8*>(base);
-    u64 o = 0;
-    auto take = [&](u64 bytes) { u8* r = p ? p + o : nullptr; o += snp_align_up(bytes, 256); return r; };
-    w.off = reinterpret_cast<u64*>(take((nb + 1) * 8));
-    w.part = reinterpret_cast<u64*>(take(scan_tiles_of(nb) * 8));
-    w.bytes = o;
+    WorkCarver k(base);
+    w.off = k.take<u64>(nb + 1);
+    w.part = k.take<u64>(scan_tiles_of(nb));
+    w.bytes = k.bytes();
     return w;
 }
 
@@ -247,26 +243,12 @@ StreamWork stream_work_layout(void* base, u32 nstreams, u32 max_spans)
     StreamWork w{};
     if (nstreams == 0) return w;
     const u64 ns = nstreams, nsp = max_spans;
-    u8* p = static_cast<u8*>(base);
-    u64 o = 0;
-    auto take = [&](u64 bytes) { u8* r = p ? p + o : nullptr; o += snp_align_up(bytes, 256); return r; };
-    w.sfirst = reinterpret_cast<u64*>(take((ns + 1) * 8));
-    w.off = reinterpret_cast<u64*>(take((ns + 1) * 8));
-    w.part = reinterpret_cast<u64*>(take(scan_tiles_of(ns) * 8));
-    w.st.total = reinterpret_cast<u64*>(take(ns * 8));
-    w.st.tail = reinterpret_cast<i32*>(take(ns * 4));
-    w.st.nc = reinterpret_cast<u32*>(take(ns * 4));
-    w.st.fail = reinterpret_cast<u32*>(take(ns * 4));
-    w.sp.count = reinterpret_cast<u32*>(take(nsp * 4));
-    w.sp.start_rel = reinterpret_cast<u32*>(take(nsp * kMaxCand * 4));
-    w.sp.exit = reinterpret_cast<u64*>(take(nsp * kMaxCand * 8));
-    w.sp.dec = reinterpret_cast<u64*>(take(nsp * kMaxCand * 8));
-    w.sp.ndata = reinterpret_cast<u32*>(take(nsp * kMaxCand * 4));
-    w.sp.stop = reinterpret_cast<i32*>(take(nsp * kMaxCand * 4));
-    w.sp.entry = reinterpret_cast<u64*>(take(nsp * 8));
-    w.sp.chunk_base = reinterpret_cast<u32*>(take(nsp * 4));
-    w.sp.out_base = reinterpret_cast<u64*>(take(nsp * 8));
-    w.bytes = o;
+    WorkCarver k(base);
+    w.sfirst = k.take<u64>(ns + 1);
+    w.off = k.take<u64>(ns + 1);
+    w.part = k.take<u64>(scan_tiles_of(ns));
+    carve_span_walk(k, ns, nsp, w.st, w.sp);
+    w.bytes = k.bytes();
     return w;
 }
 
@@ -330,13 +312,10 @@ snp_status snp_frame_decode_layout_batch(snp_ctx* c, const uint8_t* in, const ui
     const StreamWork w = stream_work_layout(d_work, ns, S);
     // the span walk of the decode call: first span slot of every stream (d_result[2] = span slots needed), candidates, one chain per stream with
     // no capacity bound (d_result[4] += spans resolved on the spot)
-    bool ok = c->check(launch_scan(ScanPieces{in_len, kSpan}, ns, w.part, w.sfirst, d_result + 2, s), "layout span scan");
+    bool ok = c->check(launch_span_scan(in_len, ns, w.part, w.sfirst, d_result + 2, s), "layout span scan");
     if (ok) {
-        hipLaunchKernelGGL(k_lay_result_init, dim3(1), dim3(64), 0, s, d_result, 5u, ns, 2u);
-        if (S) hipLaunchKernelGGL(k_fd_candidates, dim3(S), dim3(SNP_WAVE), 0, s, in, in_off, in_len, ns, w.sfirst, S, w.sp);
-        hipLaunchKernelGGL(k_fd_resolve, dim3(ns), dim3(SNP_WAVE), 0, s, in, in_off, in_len, static_cast<const u64*>(nullptr), w.sfirst, S, w.sp,
-                           w.st, d_result + 4);
-        ok = c->check(hipGetLastError(), "layout walk");
+        hipLaunchKernelGGL(k_lay_result_init, dim3(1), dim3(64), 0, s, d_result, 5u, ns, 2u);   // (after the scan wrote [2], before the resolver adds into [4])
+        ok = c->check(launch_span_walk(in, in_off, in_len, nullptr, ns, w.sfirst, S, w.sp, w.st, d_result + 4, s), "layout walk");
     }
     ok = ok && c->check(launch_scan(ScanStreamSlots{w.sfirst, w.st.total, S, align}, ns, w.part, w.off, nullptr, s), "layout scan");
     if (ok) {

@@ -1,5 +1,5 @@
 // scan_tiles.h -- exclusive prefix sums of u64 values over up to 2^32 positions, reduce-then-scan across workgroups (tiles of SNP_SCAN_TILE values):
-// the plan scans of the buffers calls (buffers.hip, buffers_decode.hip).  What is scanned is a functor V: V(i) = the value at position i, so a scan
+// the plan scans of the batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip), and owner_of, their inverse.  What is scanned is a functor V: V(i) = the value at position i, so a scan
 // reads its source as the caller's kernels see it (fragments of a length, a masked length, a packed pair of counts) with no array in between.
 // Three launches; the partial array holds one tile sum per tile (+ 1), dst holds n + 1 values (dst[n] = the grand total).
 #pragma once
@@ -107,6 +107,27 @@ hipError_t launch_scan(const V val, u32 n, u64* partial, u64* dst, u64* result, 
     hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(kScanThreads), 0, stream, partial, ntiles, dst + n, result);
     if (ntiles) hipLaunchKernelGGL((k_scan_tiles<V>), dim3(ntiles), dim3(kScanThreads), 0, stream, val, n, partial, dst);
     return hipGetLastError();
+}
+
+// values the `partial` array of a scan over n positions holds (one tile sum per tile, + 1)
+inline u64 scan_tiles_of(u64 n) { return (n + kScanTile - 1) / kScanTile + 1; }
+
+// The inverse of the scan: the last b in [0, nb) with key(b) <= t (key non-decreasing, key(0) = 0) -- the owner of slot t < key(nb).
+template <class K>
+__device__ __forceinline__ u32 owner_of(K key, u32 nb, u64 t)
+{
+    u32 lo = 0, hi = nb;
+    while (hi - lo > 1) {
+        const u32 mid = lo + (hi - lo) / 2;
+        if (key(mid) <= t) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// ... over a plain table of first slots (the dst of launch_scan)
+__device__ __forceinline__ u32 owner_of(const u64* __restrict__ first, u32 nb, u64 t)
+{
+    return owner_of([=](u32 b) { return first[b]; }, nb, t);
 }
 
 }  // namespace

@@ -1,5 +1,9 @@
 """Kernel layouts of the PRODUCT library (libsnappier_hip.so), selected per context through snp_ctx_set_option -- what the parity and fuzz tests
-parametrise over.  No test sets a SNAPPIER_HIP_* variable: the product reads no environment, and every path it contains has an option."""
+parametrise over.  No test sets a SNAPPIER_HIP_* variable: the product reads no environment, and every path it contains has an option.
+Also exported(): the snp_ names a built library exports, for the tests that hold each library to its header."""
+import re
+import subprocess
+
 from snappier_amd import _native as N
 
 COMPRESS_LAYOUTS = ["win", "win-np2", "wing", "wind", "lanes", "lanes-exact", "lanes-opts7", "lanes-opts31", "lanes-opts87-slots1", "lanes-opts215-slots1",
@@ -49,3 +53,9 @@ def set_decode_layout(ctx, decode: str, fenced=None, small_max: int = 65536):
     else:
         raise ValueError(decode)
     return ctx
+
+
+def exported(path: str) -> set[str]:
+    """The snp_ functions the shared library at `path` exports (nm -D --defined-only)."""
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return {m.group(1) for m in re.finditer(r" T (snp_[a-z0-9_]+)$", out, flags=re.M)}

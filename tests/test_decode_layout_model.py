@@ -5,7 +5,6 @@ placement rule against a brute-force loop."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -38,11 +37,9 @@ def test_header_and_binding_declare_the_new_functions():
 
 
 def test_extension_library_exports_exactly_its_header():
+    from layouts import exported
     from snappier_amd import _native as N
 
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return {m.group(1) for m in re.finditer(r" T (snp_[a-z0-9_]+)$", out, flags=re.M)}
     ext = exported(N.LAYOUT_PATH)
     assert ext == set(NAMES)
     for other in (N.PRODUCT_PATH, N.BUFFERS_PATH, N.BUFFERS_DECOMPRESS_PATH, N.FRAME_BUFFERS_PATH):
@@ -64,6 +61,26 @@ def test_workspace_functions_are_host_arithmetic():
     # the frame layout needs no chunk table: less than the decode call's workspace with the same spans and no chunk slot
     from snappier_amd import _native as N
     assert fw(1000, 5000) <= N.frame_buffers_lib().snp_frame_decode_buffers_workspace(1000, 0, 5000)
+
+
+def test_workspace_sizes_of_the_four_extensions_are_pinned():
+    """Every *_workspace function of the batch extensions returns these values: the order and the sizes of the pieces their layout functions
+    carve (work_carver.h, 256-byte pieces) are part of what a caller that sizes d_work once relies on."""
+    from snappier_amd import _native as N
+    B, D, F, Y = N.buffers_lib(), N.buffers_decompress_lib(), N.frame_buffers_lib(), N.layout_lib()
+    two = {(0, 0): (0, 0, 0, 0),
+           (1, 1): (79104, 115456, 79360, 4096),
+           (1000, 5000): (382770176, 42555136, 382790400, 718336),
+           (300000, 300000): (22968006144, 970468864, 22969206272, 51603712),
+           (7, 4294967295): (328788369922304, 203769777920, 328805549791488, 584115554048)}
+    for args, want in two.items():
+        got = (B.snp_compress_buffers_workspace(*args), D.snp_decompress_buffers_workspace(*args), F.snp_frame_encode_buffers_workspace(*args),
+               Y.snp_frame_decode_layout_workspace(*args))
+        assert got == want, (args, got)
+    for args, want in {(0, 0, 0): 0, (1, 1, 1): 6400, (1000, 70000, 5000): 3589120, (163840, 163840, 163840): 34899968}.items():
+        assert F.snp_frame_decode_buffers_workspace(*args) == want, args
+    for nb, want in {0: 0, 1: 512, 1000: 8448, 300000: 2402816}.items():
+        assert Y.snp_decompress_layout_workspace(nb) == want, nb
 
 
 def test_csharp_binding_matches_the_extension_header():

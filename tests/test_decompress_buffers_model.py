@@ -81,7 +81,7 @@ def plan(blocks, out_cap, par_min, wave_slots, max_fragments):
 
 
 def find_block(key, nb, t):
-    """find_block of buffers_decode.hip: the last b in [0, nb) with key[b] <= t."""
+    """owner_of of scan_tiles.h (buffers_decode.hip calls it with key functors): the last b in [0, nb) with key[b] <= t."""
     lo, hi = 0, nb
     while hi - lo > 1:
         mid = lo + (hi - lo) // 2
@@ -113,17 +113,13 @@ def test_batch_call_rejects_null_pointers_without_a_device():
 
 def test_header_binding_and_exports():
     """The new library exports exactly its header's functions under snp_; the product and compress-side libraries export neither."""
-    import subprocess
+    from layouts import exported
     from snappier_amd import _native as N
     declared = N.buffers_decompress_declared_symbols()
     assert declared == ["snp_decompress_buffers_batch", "snp_decompress_buffers_workspace"]
     assert not set(declared) & set(N.declared_symbols()) and not set(declared) & set(N.buffers_declared_symbols())
     L = _lib()
     assert L.snp_decompress_buffers_batch.restype is C.c_int and len(L.snp_decompress_buffers_batch.argtypes) == 13
-
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return {m.group(1) for m in re.finditer(r" T (snp_[a-z0-9_]+)$", out, flags=re.M)}
     assert exported(N.BUFFERS_DECOMPRESS_PATH) == set(declared)
     assert not exported(N.PRODUCT_PATH) & set(declared) and not exported(N.BUFFERS_PATH) & set(declared)
 

@@ -4,7 +4,6 @@ that concatenate the oracle's chunks into its framed stream, and the per-stream 
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -53,11 +52,9 @@ def test_header_and_binding_declare_the_new_functions():
 
 
 def test_extension_library_exports_exactly_its_header():
+    from layouts import exported
     from snappier_amd import _native as N
 
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return {m.group(1) for m in re.finditer(r" T (snp_[a-z0-9_]+)$", out, flags=re.M)}
     ext = exported(N.FRAME_BUFFERS_PATH)
     assert ext == set(NAMES)
     assert not exported(N.PRODUCT_PATH) & ext
