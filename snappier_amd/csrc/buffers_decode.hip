@@ -3,12 +3,14 @@
 // with nothing read back to the host; the other blocks go through snp_decompress_batch's own launch sequence.  Built into
 // libsnappier_hip_buffers_decompress.so (C-ABI: include/snappier_hip_buffers_decompress.h), linked against libsnappier_hip.so.
 // The steps, all on the context's stream:
-//   classify  one thread per block: varint preamble, candidate or not (the rule of snp_try_decompress plus a stream-length bound)
+//   classify  one thread per block: varint preamble (snp_rules.h), candidate or not (the rule of snp_try_decompress plus a stream-length bound)
 //   plan      scans (scan_tiles.h): the candidates' declared bytes (the makespan rule needs their sum), the fragments of the blocks chosen for
 //             splitting (d_result[0]; admitted in buffer order while they fit max_fragments), the chunks and the count of the admitted blocks;
 //             then one thread per block: masked in_len / out_cap (0 for a split block) and the block's tag-index control words
 //   index     k_tag_cand, k_tag_scan and the look-back kernel of tag_index.hip over every split block at once: the first and the last take one
-//             global ticket in block-major chunk order, the scan runs as persistent workgroups that take blocks, each with its own RunCache
+//             global ticket in block-major chunk order, the scan runs as persistent workgroups that take blocks, each with its own RunCache;
+//             the kernels here are drivers of the same bodies as tag_index.hip's (tag_index_device.h: cand_chunk, scan_pass / fix_pass,
+//             look_back_chunk, fragment_start)
 //   decode    the fragment table (k_fragment_starts over all blocks), one launch of the fragment decoder, then snp_ctx::launch_decompress over
 //             all blocks with the masked lengths (a split block is a no-op there)
 //   finalize  a split block is OK when all its fragments are; the others go on a list that the list decoder decodes one wavefront each
@@ -32,7 +34,6 @@ constexpr u32 kCtlFail = 12;
 constexpr u32 kGlobWords = 256;
 constexpr u32 kGlobList = 128;
 
-__device__ __forceinline__ u32 chunks_of(u32 n, u32 hb) { return (n - hb + kChunk - 1) / kChunk; }
 __device__ __forceinline__ bool admitted(const u64* __restrict__ first, u32 b, u32 max_fragments)
 {
     return first[b + 1] > first[b] && first[b + 1] <= max_fragments;
@@ -54,16 +55,9 @@ __global__ __launch_bounds__(256) void k_bd_classify(const u8* __restrict__ in, 
     if (b >= nb) return;
     const u8* const p = in + in_off[b];
     const u32 n = in_len[b];
-    u32 expected = 0, hb = 0, shift = 0;
-    bool clean = false;
-    for (u32 i = 0; i < 5 && i < n; ++i) {                                // VarIntEncoding.Read.cs:38-79 (as decompress_spans reads it)
-        const u32 ch = p[i], val = ch & 0x7fu;
-        if (val & ~(0xffffffffu >> shift)) break;
-        expected |= val << shift;
-        shift += 7;
-        hb = i + 1;
-        if (ch < 128) { clean = true; break; }
-    }
+    const snp_preamble pre = snp_read_preamble(p, n);                     // (as decompress_spans reads it)
+    const u32 expected = pre.value, hb = pre.bytes;
+    const bool clean = pre.end == SNP_PRE_DONE;
     const u64 max_comp = 38ull + expected + expected / 6;                 // snp_max_compressed_length (which is -1 above 2^31 - 1)
     const bool cand = clean && par_min && expected >= par_min && expected <= out_cap[b] && n > hb && max_comp <= 0x7fffffffull && n <= max_comp;
     decl[b] = cand ? expected : 0u;
@@ -90,12 +84,12 @@ struct ScanAdmitted {
     __device__ __forceinline__ u64 operator()(u64 i) const
     {
         const u32 b = static_cast<u32>(i);
-        return admitted(first, b, max_fragments) ? (static_cast<u64>(chunks_of(in_len[b], hbv[b])) << 32) | 1u : 0;
+        return admitted(first, b, max_fragments) ? (static_cast<u64>(snp_tag_chunks(in_len[b], hbv[b])) << 32) | 1u : 0;
     }
 };
 
-// masked lengths for the blocks' own decode; a split block's control words (the look-back flag set up front for a stream of >= 85 % of its
-// output: snp_tag_index_look_back_only)
+// masked lengths for the blocks' own decode; a split block's control words (the look-back flag set up front by the rule of
+// snp_tag_index_look_back_only)
 __global__ __launch_bounds__(256) void k_bd_begin(const u32* __restrict__ in_len, const u32* __restrict__ out_cap, u32 nb, const u64* __restrict__ first,
                                                  u32 max_fragments, const u32* __restrict__ decl, u32* __restrict__ m_in_len, u32* __restrict__ m_out_cap,
                                                  u32* __restrict__ ctl, u32* __restrict__ glob)
@@ -107,7 +101,7 @@ __global__ __launch_bounds__(256) void k_bd_begin(const u32* __restrict__ in_len
     m_out_cap[b] = split ? 0u : out_cap[b];
     if (split) {
         u32* const c = ctl + static_cast<u64>(b) * kCtlWords;
-        const bool lbo = static_cast<u64>(in_len[b]) * 100 >= static_cast<u64>(decl[b]) * 85;
+        const bool lbo = snp_look_back_only(in_len[b], decl[b]);
         for (u32 i = 0; i < kCtlWords; ++i) c[i] = i == 2 && lbo ? 1u : 0u;
         if (lbo) glob[3] = 1;
     }
@@ -141,7 +135,7 @@ __device__ __forceinline__ Split split_block(u32 b, const u8* in, const u64* in_
     s.n = in_len[b];
     s.hb = hbv[b];
     s.k = 0;
-    s.nchunks = chunks_of(s.n, s.hb);
+    s.nchunks = snp_tag_chunks(s.n, s.hb);
     s.slot = slot_of(packed, b);
     s.ctl = reinterpret_cast<ScanCtl*>(ctl + static_cast<u64>(b) * kCtlWords);
     return s;
@@ -149,7 +143,7 @@ __device__ __forceinline__ Split split_block(u32 b, const u8* in, const u64* in_
 
 // k_tag_cand over every chunk of every split block: persistent workgroups take one ticket at a time, in block-major chunk order, so a workgroup
 // only ever waits on a neighbour with an earlier ticket (a block's chunk 0 never waits).  Look-back-only blocks are skipped.  The body per chunk
-// is k_tag_cand's (tag_index.hip keeps its own copy: the single-block kernels compile to the code they always had).
+// is k_tag_cand's: cand_chunk (tag_index_device.h).
 __global__ __launch_bounds__(kThreads) void k_bd_tag_cand(const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len,
                                                          const u32* __restrict__ hbv, u32 nb, const u64* __restrict__ packed, u32* __restrict__ ctl_all,
                                                          CandTable* __restrict__ tables_all, CandHandoff* __restrict__ hand_all, u32* __restrict__ glob)
@@ -172,83 +166,10 @@ __global__ __launch_bounds__(kThreads) void k_bd_tag_cand(const u8* __restrict__
         __syncthreads();
         const u32 tk = s_ticket;
         if (tk >= total) return;
-        Split B = split_block(s_b, in, in_off, in_len, hbv, packed, ctl_all);
-        if (B.ctl->fallback == 0) {
-            const u8* const src = B.src;
-            const u32 n = B.n, hb = B.hb, k = static_cast<u32>(tk - (packed[s_b] >> 32));
-            CandTable* const tables = tables_all + B.slot;
-            CandHandoff* const hand = hand_all + B.slot;
-            const u64 base = hb + static_cast<u64>(k) * kChunk;
-            const u64 end = base + kChunk;
-            build_table(T, s_raw, src, n, base);
-            if (threadIdx.x < kProbe) {
-                u32 rip[kSubs + 1], rop[kSubs + 1];
-                const u64 start = base + threadIdx.x;
-                u32 land = kBadIp;
-                if (start < n) {
-                    walk_chunk(T, n, base, static_cast<u32>(start), 0u, rip, rop);
-                    land = rip[kSubs];
-                }
-                s_land[threadIdx.x] = (land != kBadIp && land >= end && land < end + kChunk && land < n) ? land : kBadIp;
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                CandHandoff* const h = hand + k + 1;
-                u32 cnt = 0;
-                u32 keys[kMaxCand];
-                for (u32 i = 0; i < kProbe && cnt != kWide; ++i) {
-                    const u32 v = s_land[i];
-                    if (v == kBadIp) continue;
-                    bool seen = false;
-#pragma unroll
-                    for (u32 c = 0; c < kMaxCand; ++c) seen = seen || (c < cnt && keys[c] == v);
-                    if (seen) continue;
-                    if (cnt == kMaxCand) { cnt = kWide; break; }
-#pragma unroll
-                    for (u32 c = 0; c < kMaxCand; ++c)
-                        if (c == cnt) keys[c] = v;
-                    ++cnt;
-                }
-#pragma unroll
-                for (u32 c = 0; c < kMaxCand; ++c) {
-                    h->key[c] = keys[c];
-                    s_next_key[c] = keys[c];
-                }
-                s_next_ncand = cnt;
-                h->ncand = cnt;
-                __hip_atomic_store(&h->ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                if (k == 0) {
-                    s_ncand = 1;
-                    s_key[0] = hb;
-                } else {
-                    const CandHandoff* const m = hand + k;
-                    while (__hip_atomic_load(&m->ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(1);
-                    const u32 nc = m->ncand;
-                    s_ncand = nc;
-                    for (u32 c = 0; c < kMaxCand && nc != kWide && c < nc; ++c) s_key[c] = m->key[c];
-                }
-            }
-            __syncthreads();
-            const u32 nc = s_ncand;
-            CandTable* const t = tables + k;
-            if (threadIdx.x == 0) t->ncand = nc;
-            if (nc != kWide && threadIdx.x < nc) {
-                u32 rip[kSubs + 1], rop[kSubs + 1];
-                const u32 key = s_key[threadIdx.x];
-                walk_chunk(T, n, base, key, 0u, rip, rop);
-                t->key[threadIdx.x] = key;
-                for (u32 sc = 1; sc <= kSubs; ++sc) {
-                    t->ip[threadIdx.x][sc - 1] = rip[sc];
-                    t->op[threadIdx.x][sc - 1] = rop[sc];
-                }
-                const u32 out = rip[kSubs];
-                u32 nx = out == kBadIp ? kFail : out == n ? kDone : kByPos;
-                if (nx == kByPos && s_next_ncand != kWide)
-                    for (u32 c = 0; c < kMaxCand; ++c)
-                        if (c < s_next_ncand && s_next_key[c] == out) nx = c;
-                t->nxt[threadIdx.x] = nx;
-            }
-        }
+        const Split B = split_block(s_b, in, in_off, in_len, hbv, packed, ctl_all);
+        if (B.ctl->fallback == 0)
+            cand_chunk(T, s_raw, s_land, s_ncand, s_key, s_next_ncand, s_next_key, B.src, B.n, B.hb, static_cast<u32>(tk - (packed[s_b] >> 32)),
+                       tables_all + B.slot, hand_all + B.slot);
         __syncthreads();                                                  // (the LDS of this chunk is read until here)
     }
 }
@@ -292,7 +213,8 @@ __global__ __launch_bounds__(kThreads) void k_bd_tag_scan(const u8* __restrict__
     }
 }
 
-// The look-back kernel (k_tag_index) over the chunks of the blocks that want it, by one global ticket in block-major chunk order as above.
+// The look-back kernel (k_tag_index) over the chunks of the blocks that want it, by one global ticket in block-major chunk order as above; the
+// body per chunk is look_back_chunk (tag_index_device.h).
 __global__ __launch_bounds__(kThreads) void k_bd_tag_look_back(const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len,
                                                               const u32* __restrict__ hbv, u32 nb, const u64* __restrict__ packed, u32* __restrict__ ctl_all,
                                                               u64* __restrict__ looked, u32* __restrict__ glob)
@@ -312,36 +234,8 @@ __global__ __launch_bounds__(kThreads) void k_bd_tag_look_back(const u8* __restr
         const u32 tk = s_ticket;
         if (tk >= total) return;
         const Split B = split_block(s_b, in, in_off, in_len, hbv, packed, ctl_all);
-        if (__hip_atomic_load(&B.ctl->fallback, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-            const u32 n = B.n, hb = B.hb, k = static_cast<u32>(tk - (packed[s_b] >> 32));
-            u64* const entries = looked + B.slot * kSubs;
-            const u64 base = hb + static_cast<u64>(k) * kChunk;
-            build_table(T, s_raw, B.src, n, base);
-            if (threadIdx.x == 0) {
-                u64 ent;
-                if (k == 0) {
-                    ent = kValid | pack(0, hb);
-                } else {
-                    while ((ent = __hip_atomic_load(&entries[static_cast<u64>(k) * kSubs], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0)
-                        __builtin_amdgcn_s_sleep(1);
-                }
-                u32 ip = static_cast<u32>(ent);
-                u32 op = static_cast<u32>(ent >> 32) & 0x7fffffffu;
-                for (u32 sc = 0; sc < kSubs; ++sc) {
-                    if (sc) entries[static_cast<u64>(k) * kSubs + sc] = kValid | pack(op, ip);
-                    else if (k == 0) entries[0] = ent;
-                    const u64 sub_end = base + static_cast<u64>(sc + 1) * kSub;
-                    if (ip == kBadIp || ip >= n || ip >= sub_end) continue;
-                    const u64 e = T[ip - base];
-                    const u32 nx = static_cast<u32>(e);
-                    const u64 sum = static_cast<u64>(op) + (e >> 32);
-                    if (nx >= kFar || base + nx > n || sum > 0x7fffffffull) { ip = kBadIp; continue; }
-                    ip = static_cast<u32>(base + nx);
-                    op = static_cast<u32>(sum);
-                }
-                __hip_atomic_store(&entries[static_cast<u64>(k + 1) * kSubs], kValid | pack(op, ip), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        if (__hip_atomic_load(&B.ctl->fallback, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
+            look_back_chunk(T, s_raw, B.src, B.n, B.hb, static_cast<u32>(tk - (packed[s_b] >> 32)), looked + B.slot * kSubs);
         __syncthreads();                                                  // (the LDS of this chunk is read until here)
     }
 }
@@ -364,28 +258,16 @@ __global__ __launch_bounds__(256) void k_bd_fragment_starts(const u64* __restric
         if (first[b + 1] <= max_fragments) {
             const u32 n = in_len[b], expected = decl[b];
             const u64 slot = slot_of(packed, b);
-            const u32 nent = chunks_of(n, hbv[b]) * kSubs + 1;
+            const u32 nent = snp_tag_chunks(n, hbv[b]) * kSubs + 1;
             const u64* const entries = (ctl_all[static_cast<u64>(b) * kCtlWords + 2] ? looked : scanned) + slot * kSubs;
             const u32 target = static_cast<u32>(f - first[b]) * SNP_BLOCK_SIZE;
-            const u64 last = entries[nent - 1];
-            const bool good = static_cast<u32>(last) == n && (static_cast<u32>(last >> 32) & 0x7fffffffu) == expected;
+            const FragStart fs = fragment_start(entries, nent, n, expected, target);
             owner = b;
             oo = out_off[b] + target;
             cap = expected - target < SNP_BLOCK_SIZE ? expected - target : SNP_BLOCK_SIZE;
-            io = in_off[b];
-            if (good) {                                                   // (else the fragment decoder reports "incomplete": the block falls back)
-                u32 lo = 0, hi = nent - 1;
-                while (lo < hi) {
-                    const u32 mid = (lo + hi + 1) / 2;
-                    if ((static_cast<u32>(entries[mid] >> 32) & 0x7fffffffu) <= target) lo = mid;
-                    else hi = mid - 1;
-                }
-                const u64 e = entries[lo];
-                const u32 ip = static_cast<u32>(e);
-                io += ip;
-                il = n - ip;
-                skip = target - (static_cast<u32>(e >> 32) & 0x7fffffffu);
-            }
+            io = in_off[b] + fs.ip;
+            il = fs.good ? n - fs.ip : 0u;                                // (0: the fragment decoder reports "incomplete", the block falls back)
+            skip = fs.skip;
         }
     }
     f_in_off[f] = io;

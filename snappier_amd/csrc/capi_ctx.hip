@@ -399,22 +399,11 @@ int64_t snp_max_compressed_length(int64_t n)            // Snappy.GetMaxCompress
 snp_status snp_get_uncompressed_length(const uint8_t* in, size_t n, uint32_t* out_len, uint32_t* out_header_bytes)
 {
     if (!in && n) return SNP_ERR_BAD_ARG;
-    u32 result = 0;
-    int shift = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const u8 c = in[i];
-        const u32 val = c & 0x7fu;
-        if (val & ~(0xffffffffu >> shift)) return SNP_ERR_BAD_LENGTH;
-        result |= val << shift;
-        shift += 7;
-        if (c < 128) {
-            if (out_len) *out_len = result;
-            if (out_header_bytes) *out_header_bytes = static_cast<u32>(i + 1);
-            return SNP_OK;
-        }
-        if (shift >= 32) return SNP_ERR_BAD_LENGTH;
-    }
-    return SNP_ERR_BAD_LENGTH;
+    const snp_preamble pre = snp_read_preamble(in, n);
+    if (pre.end != SNP_PRE_DONE) return SNP_ERR_BAD_LENGTH;
+    if (out_len) *out_len = pre.value;
+    if (out_header_bytes) *out_header_bytes = pre.bytes;
+    return SNP_OK;
 }
 
 int64_t snp_frame_max_encoded_length(int64_t n)

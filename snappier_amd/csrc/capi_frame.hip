@@ -171,7 +171,6 @@ struct ChunkScan {
     u64 total = 0;
     snp_status tail = SNP_OK;   // error met after the chunks listed above (they are still decoded and checked first)
 };
-static inline u64 snp_max_expansion(u64 body_bytes) { return (body_bytes / 3 + 1) * 64; }
 static void scan_chunks(const u8* in, size_t n, ChunkScan& cs)
 {
     size_t ip = 0;
@@ -191,8 +190,7 @@ static void scan_chunks(const u8* in, size_t n, ChunkScan& cs)
                 return;
             }
             if (dec > 0x7fffffffu) { cs.tail = SNP_ERR_BAD_LENGTH; return; }
-            // No tag expands more than 3 bytes -> 64 (a copy-2 of length 64): a chunk that declares more than its body can
-            // possibly produce is "Incomplete Snappy block." whatever its tags say -- and must not size any allocation.
+            // a chunk that declares more than its body can possibly produce (snp_rules.h) is "Incomplete Snappy block."
             if (type == 0x00 && dec > snp_max_expansion(size - 4 - hb)) { cs.tail = SNP_ERR_INCOMPLETE; return; }
             cs.type.push_back(static_cast<u8>(type));
             cs.body_off.push_back(ip + 4);

@@ -151,16 +151,9 @@ snp_status decompress_spans(snp_ctx* c, const HostSpans& in_spans, size_t n, uin
     // A large block: one wavefront per 64 KiB output fragment, fragment starts from the tag index (tag_index.hip).
     // Taken only for a clean preamble that fits the output; any fragment that does not come back OK (foreign streams
     // whose copies cross fragments, malformed data) sends the whole block to the single-wavefront decoder below.
-    u32 expected = 0, hb = 0, shift = 0;
-    bool clean = false;
-    for (u32 i = 0; i < 5 && i < n; ++i) {                                // VarIntEncoding.Read.cs:38-79
-        const u32 ch = in[i], val = ch & 0x7fu;
-        if (val & ~(0xffffffffu >> shift)) break;
-        expected |= val << shift;
-        shift += 7;
-        hb = i + 1;
-        if (ch < 128) { clean = true; break; }
-    }
+    const snp_preamble pre = snp_read_preamble(in, n);
+    const u32 expected = pre.value, hb = pre.bytes;
+    const bool clean = pre.end == SNP_PRE_DONE;
     const bool large = clean && c->par_min && expected >= c->par_min && expected <= cap32 && n > hb;
     const u32 nf = large ? (expected + SNP_BLOCK_SIZE - 1) / SNP_BLOCK_SIZE : 0;
     // fragment table: in_off, out_off (u64) ; in_len, out_cap, skip, out_len (u32) ; status (i32)

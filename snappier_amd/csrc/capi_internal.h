@@ -25,7 +25,7 @@
 #include <utility>
 #include <vector>
 
-#include "snp_device.h"
+#include "snp_rules.h"
 
 extern "C" {
 hipError_t snp_launch_decompress(const u8*, const u64*, const u32*, u32, u8*, const u64*, const u32*, u32*, i32*,

@@ -159,7 +159,7 @@ __device__ __forceinline__ bool block_begin(SNP_D_PARAMS, const u32 b, const u32
     if (FRAG) {
         B.expected = B.skip + B.cap;                     // no preamble: the fragment ends `cap` bytes after its start
     } else {
-        const u64 q = win_fetch(B.w, B.mis, lane);
+        const u64 q = win_fetch(B.w, B.mis, lane);                     // the preamble: restates snp_read_preamble (snp_rules.h), which changes the decoders' listings
         u32 shift = 0, result = 0;
         bool done = false;
         for (u32 i = 0; i < 5 && !done; ++i) {

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(SNP_WAVE) void k_decompress_small(const u8* __restr
     const u8* src = in + in_off[b];
     u8* dst = out + out_off[b];
     u32 ip = 0, op = 0, expected = 0;
-    if (!redo) {                                                        // varint preamble  VarIntEncoding.Read.cs:38-79
+    if (!redo) {                                                        // varint preamble: restates snp_read_preamble (snp_rules.h), which changes this kernel's listing
         u32 shift = 0;
         bool done = false;
         while (ip < n && ip < 5) {
@@ -247,7 +247,7 @@ __device__ __forceinline__ void decompress_teams(SNP_T_PARAMS)
         asm volatile("" ::: "memory");                                  // (LDS operations of a wave execute in order)
         u32 ip = 0, expected = 0;
         op = 0;
-        if (now) {                                                      // varint preamble  VarIntEncoding.Read.cs:38-79
+        if (now) {                                                      // varint preamble: restates snp_read_preamble (snp_rules.h), which changes these kernels' listings
             u32 shift = 0;
             bool done = false;
             while (ip < n && ip < 5) {

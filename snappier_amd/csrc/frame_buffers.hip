@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void k_fd_pad(u32 ns, const u64* __restrict__ 
         r.type[c] = 1;
         r.body_off[c] = 0;
         r.body_len[c] = 0;
-        r.crc[c] = kEmptyMaskedCrcS;
+        r.crc[c] = kEmptyMaskedCrc;
         r.out_off[c] = 0;
         r.out_cap[c] = 0;
     }

@@ -1,15 +1,16 @@
 // frame_hop_device.h -- one hop of a framed stream's chunk-header walk, and the span walk built on it: the device code that the one-stream
-// header walk (frame_scan.hip, snp_frame_decode_device) and the batched one (frame_buffers.hip, snp_frame_decode_buffers_batch) share.
-// The rules of one hop (frame_hop) are those of the host walk in capi_frame.hip (scan_chunks); moved here from frame_scan.hip unchanged.
+// header walks (the serial one of framing.hip, k_frame_scan, and the span walk of frame_scan.hip: snp_frame_decode_device) and the batched
+// one (frame_buffers.hip, snp_frame_decode_buffers_batch) share.  The rules of one hop (frame_hop) are those of the host walk in
+// capi_frame.hip (scan_chunks); the block preamble and the expansion bound inside it are snp_rules.h's.
 #pragma once
-#include "snp_device.h"
+#include "snp_rules.h"
 
 namespace {
 
 constexpr u64 kSpan = 1ull << 20;
 constexpr u32 kWindow = 80 * 1024;          // > 8 + MaxCompressedLength(65536): the next header after any spec-sized data chunk
 constexpr u32 kMaxCand = 4;                 // candidates kept per span (the lowest plausible positions of its window)
-constexpr u32 kEmptyMaskedCrcS = 0xa282ead8u;   // crc32c_mask(crc32c of no bytes)
+constexpr u32 kEmptyMaskedCrc = 0xa282ead8u;   // crc32c_mask(crc32c of no bytes)
 constexpr u64 kNoEntry = ~0ull;
 
 enum HopKind : u32 { HOP_DATA = 0, HOP_SKIP = 1, HOP_END = 2, HOP_ERR = 3 };
@@ -44,22 +45,11 @@ __device__ __forceinline__ Hop frame_hop(const u8* __restrict__ in, u64 n, u64 i
         if (size < 4) { h.kind = HOP_ERR; h.err = SNP_ERR_TRUNCATED_STREAM; return h; }
         u32 dec = size - 4;
         if (t == 0) {                                                   // block preamble  VarIntEncoding.Read.cs:38-79
-            const u64 pre = b[2] | (static_cast<u64>(b[3]) << 32);
-            const u32 avail = size - 4 < 5 ? size - 4 : 5;
-            u32 result = 0, shift = 0;
-            bool done = false, bad = false;
-            for (u32 i = 0; i < avail && !done && !bad; ++i) {
-                const u32 c = static_cast<u32>(pre >> (8 * i)) & 0xffu;
-                const u32 val = c & 0x7fu;
-                if (val & ~(0xffffffffu >> shift)) { bad = true; break; }
-                result |= val << shift;
-                shift += 7;
-                if (c < 128) done = true;
-            }
-            if (bad || !done || result > 0x7fffffffu) { h.kind = HOP_ERR; h.err = SNP_ERR_BAD_LENGTH; return h; }
-            dec = result;
-            // no tag expands more than 3 bytes -> 64: such a chunk can only end "Incomplete Snappy block." (capi_frame.hip scan_chunks)
-            if (static_cast<u64>(dec) > (static_cast<u64>(size - 4 - (shift / 7)) / 3 + 1) * 64) { h.kind = HOP_ERR; h.err = SNP_ERR_INCOMPLETE; return h; }
+            const snp_preamble pre = snp_read_preamble(b[2] | (static_cast<u64>(b[3]) << 32), size - 4);
+            if (pre.end != SNP_PRE_DONE || pre.value > 0x7fffffffu) { h.kind = HOP_ERR; h.err = SNP_ERR_BAD_LENGTH; return h; }
+            dec = pre.value;
+            // (such a chunk can only end "Incomplete Snappy block.": capi_frame.hip scan_chunks)
+            if (dec > snp_max_expansion(size - 4 - pre.bytes)) { h.kind = HOP_ERR; h.err = SNP_ERR_INCOMPLETE; return h; }
         }
         h.kind = HOP_DATA;
         h.type = t;

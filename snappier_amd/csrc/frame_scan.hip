@@ -200,7 +200,7 @@ __global__ __launch_bounds__(SNP_WAVE) void k_span_emit(const u8* __restrict__ i
             type[r] = 1;
             body_off[r] = 0;
             body_len[r] = 0;
-            crc[r] = kEmptyMaskedCrcS;
+            crc[r] = kEmptyMaskedCrc;
             out_off[r] = total;
             out_cap[r] = 0;
         }

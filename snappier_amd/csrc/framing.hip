@@ -1,7 +1,7 @@
 // framing.hip -- device side of the Snappy framing format (SnappyStreamCompressor.cs:18-21,194-261) and the
 // segment gather used to concatenate independently compressed fragments (SnappyCompressor.cs:40-80 writes them
 // back to back).  Pure data movement: 256-thread workgroups, 16 B per lane.
-#include "snp_device.h"
+#include "frame_hop_device.h"
 
 namespace {
 
@@ -108,12 +108,10 @@ __global__ __launch_bounds__(256) void k_frame_emit(const u8* __restrict__ raw, 
 
 // ---- device-side chunk-header walk (SnappyStreamDecompressor.ReadChunkHeader / Decompress  :53-199,215-289) -----
 // A framed stream carries no index: every header gives the position of the next one, so the walk is a serial chain of
-// ~64 KiB hops (one 16-byte load per chunk: type, 24-bit size, masked CRC and the first bytes of the block preamble).
-// One lane walks; the table it writes is exactly what the host walk in capi_frame.hip produces.  Entries past the last data
+// ~64 KiB hops (frame_hop of frame_hop_device.h: one 16-byte load per chunk -- type, 24-bit size, masked CRC and the first bytes of the block
+// preamble).  One lane walks; the table it writes is exactly what the host walk in capi_frame.hip produces.  Entries past the last data
 // chunk are filled as empty uncompressed chunks so that the decode and CRC launches can run over max_chunks without
 // knowing the count on the host.
-constexpr u32 kEmptyMaskedCrc = 0xa282ead8u;      // crc32c_mask(crc32c of no bytes = 0)
-
 __global__ __launch_bounds__(SNP_WAVE) void k_frame_scan(const u8* __restrict__ in, u64 n, u64 cap, u32 max_chunks,
                                                         u8* __restrict__ type, u64* __restrict__ body_off,
                                                         u32* __restrict__ body_len, u32* __restrict__ crc,
@@ -126,54 +124,22 @@ __global__ __launch_bounds__(SNP_WAVE) void k_frame_scan(const u8* __restrict__ 
         u64 ip = 0, total = 0;
         u32 nc = 0;
         i32 tail = SNP_OK;
-        while (ip < n) {
-            if (n - ip < 4) { tail = SNP_ERR_TRUNCATED_STREAM; break; }
-            u32 b[4] = {0, 0, 0, 0};                                    // 16 bytes at ip (fewer at the very end)
-            if (n - ip >= 16) {
-                const snp_u128_unaligned q = *reinterpret_cast<const snp_u128_unaligned*>(in + ip);
-                b[0] = q.v[0]; b[1] = q.v[1]; b[2] = q.v[2]; b[3] = q.v[3];
-            } else {
-                for (u32 i = 0; i < n - ip; ++i) b[i >> 2] |= static_cast<u32>(in[ip + i]) << (8 * (i & 3));
-            }
-            const u32 t = b[0] & 0xffu;
-            const u32 size = b[0] >> 8;                                 // :64-65
-            ip += 4;
-            if (n - ip < size) { tail = SNP_ERR_TRUNCATED_STREAM; break; }
-            if (t <= 1) {
-                if (size < 4) { tail = SNP_ERR_TRUNCATED_STREAM; break; }
-                u32 dec = size - 4;
-                if (t == 0) {                                           // block preamble  VarIntEncoding.Read.cs:38-79
-                    const u64 pre = b[2] | (static_cast<u64>(b[3]) << 32);
-                    const u32 avail = size - 4 < 5 ? size - 4 : 5;
-                    u32 result = 0, shift = 0;
-                    bool done = false, bad = false;
-                    for (u32 i = 0; i < avail && !done && !bad; ++i) {
-                        const u32 c = static_cast<u32>(pre >> (8 * i)) & 0xffu;
-                        const u32 val = c & 0x7fu;
-                        if (val & ~(0xffffffffu >> shift)) { bad = true; break; }
-                        result |= val << shift;
-                        shift += 7;
-                        if (c < 128) done = true;
-                    }
-                    if (bad || !done || result > 0x7fffffffu) { tail = SNP_ERR_BAD_LENGTH; break; }
-                    dec = result;
-                    // no tag expands more than 3 bytes -> 64: such a chunk can only end "Incomplete Snappy block." (capi_frame.hip scan_chunks)
-                    if (static_cast<u64>(dec) > (static_cast<u64>(size - 4 - (shift / 7)) / 3 + 1) * 64) { tail = SNP_ERR_INCOMPLETE; break; }
-                }
+        for (;;) {
+            const Hop h = frame_hop(in, n, ip);
+            if (h.kind == HOP_END) break;
+            if (h.kind == HOP_ERR) { tail = h.err; break; }
+            if (h.kind == HOP_DATA) {
                 if (nc == max_chunks) { tail = SNP_ERR_OUTPUT_TOO_SMALL; break; }   // chunk table full
-                type[nc] = static_cast<u8>(t);
-                body_off[nc] = ip + 4;
-                body_len[nc] = size - 4;
-                crc[nc] = b[1];                                         // ReadChunkCrc  :260-289
+                type[nc] = static_cast<u8>(h.type);
+                body_off[nc] = ip + 8;
+                body_len[nc] = h.body_len;
+                crc[nc] = h.crc;
                 out_off[nc] = total;
-                out_cap[nc] = dec;
-                total += dec;
+                out_cap[nc] = h.dec;
+                total += h.dec;
                 ++nc;
-            } else if (t < 0x80) {                                      // :182-185
-                tail = SNP_ERR_CHUNK_TYPE;
-                break;
-            }                                                           // 0x80..0xff skipped unvalidated  :187-196
-            ip += size;
+            }
+            ip = h.next;
         }
         if (total > cap) { tail = SNP_ERR_OUTPUT_TOO_SMALL; nc = 0; total = 0; }   // nothing is decoded
         hdr[0] = total;

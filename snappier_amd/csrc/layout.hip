@@ -62,24 +62,14 @@ __global__ __launch_bounds__(256) void k_bl_probe(const u8* __restrict__ in, con
     if (b >= nb) return;
     const u32 n = in_len[b];
     const u8* const p = in + in_off[b];
-    const u32 avail = n < 5 ? n : 5;
-    u32 result = 0, shift = 0, hb = 0;
-    bool done = false;
-    for (u32 i = 0; i < avail; ++i) {
-        const u32 c = p[i];
-        const u32 val = c & 0x7fu;
-        if (val & ~(0xffffffffu >> shift)) break;
-        result |= val << shift;
-        shift += 7;
-        if (c < 128) { done = true; hb = i + 1; break; }
-    }
+    const snp_preamble pre = snp_read_preamble(p, n);
     i32 st = SNP_ERR_BAD_LENGTH;
     u32 dec = 0;
-    if (done) {
-        // no tag expands more than 3 bytes -> 64: a block that declares more can only end "Incomplete Snappy block." (capi_frame.hip scan_chunks)
-        const bool fits = static_cast<u64>(result) <= (static_cast<u64>(n - hb) / 3 + 1) * 64;
+    if (pre.end == SNP_PRE_DONE) {
+        // (a block that declares more can only end "Incomplete Snappy block.": capi_frame.hip scan_chunks)
+        const bool fits = pre.value <= snp_max_expansion(n - pre.bytes);
         st = fits ? SNP_OK : SNP_ERR_INCOMPLETE;
-        dec = fits ? result : 0;
+        dec = fits ? pre.value : 0;
     }
     declared[b] = dec;
     status[b] = st;

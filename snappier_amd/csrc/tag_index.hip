@@ -31,7 +31,7 @@
 // fragment decoder (k_decompress<.., FRAG = true>) then parses at most 4 KiB of tags before its fragment begins.
 // Anything that is not a well-formed stream ending exactly at (n, declared length) marks the table irregular and the
 // caller falls back to the single-wavefront decoder, which owns the error semantics.
-#include "tag_index_device.h"                  // build_table, walk_chunk, the candidate tables, scan_pass, fix_pass (shared with buffers_decode.hip)
+#include "tag_index_device.h"                  // every step's body (shared with buffers_decode.hip): the kernels below are their single-block drivers
 
 namespace {
 
@@ -46,38 +46,7 @@ __global__ __launch_bounds__(kThreads) void k_tag_index(const u8* __restrict__ s
     __syncthreads();
     const u32 k = s_chunk;
     if (k >= nchunks) return;
-    const u64 base = hb + static_cast<u64>(k) * kChunk;               // stream offset of this chunk
-
-    build_table(T, s_raw, src, n, base);
-    // ---- 2. look-back: the true entry of this chunk, through its sub-chunks, to the entry of the next chunk -------
-    if (threadIdx.x == 0) {
-        u64 ent;
-        if (k == 0) {
-            ent = kValid | pack(0, hb);                                  // the first tag follows the varint preamble
-        } else {
-            // The hand-off IS this one 8-byte word (valid bit | output offset | stream position): a relaxed agent-scope load
-            // (L2-served) and store are enough -- no payload behind a flag, so no acquire/release and no cache invalidation per
-            // poll (MI355X_MICROARCH.md, hand-off price list: acquire polling costs 2-3x per hop).  Measured: 4.6 -> 0.84 us per hop
-            // (k_tag_index over a 0.29 GiB stream: 86 -> 15.7 ms).
-            while ((ent = __hip_atomic_load(&entries[static_cast<u64>(k) * kSubs], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0)
-                __builtin_amdgcn_s_sleep(1);
-        }
-        u32 ip = static_cast<u32>(ent);                                   // stream offset of a tag start (or n, or kBadIp)
-        u32 op = static_cast<u32>(ent >> 32) & 0x7fffffffu;               // output bytes produced before it
-        for (u32 sc = 0; sc < kSubs; ++sc) {
-            if (sc) entries[static_cast<u64>(k) * kSubs + sc] = kValid | pack(op, ip);
-            else if (k == 0) entries[0] = ent;
-            const u64 sub_end = base + static_cast<u64>(sc + 1) * kSub;
-            if (ip == kBadIp || ip >= n || ip >= sub_end) continue;       // finished, irregular, or a literal jumps over this sub-chunk
-            const u64 e = T[ip - base];
-            const u32 nx = static_cast<u32>(e);
-            const u64 sum = static_cast<u64>(op) + (e >> 32);
-            if (nx >= kFar || base + nx > n || sum > 0x7fffffffull) { ip = kBadIp; continue; }
-            ip = static_cast<u32>(base + nx);
-            op = static_cast<u32>(sum);
-        }
-        __hip_atomic_store(&entries[static_cast<u64>(k + 1) * kSubs], kValid | pack(op, ip), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    look_back_chunk(T, s_raw, src, n, hb, k, entries);
 }
 
 __global__ __launch_bounds__(kThreads) void k_tag_cand(const u8* __restrict__ src, u32 n, u32 hb, u32 nchunks, CandTable* __restrict__ tables,
@@ -95,78 +64,7 @@ __global__ __launch_bounds__(kThreads) void k_tag_cand(const u8* __restrict__ sr
     __syncthreads();
     const u32 k = s_chunk;
     if (k >= nchunks) return;
-    const u64 base = hb + static_cast<u64>(k) * kChunk;
-    const u64 end = base + kChunk;
-    build_table(T, s_raw, src, n, base);
-    // where the walks that enter at the chunk's first bytes leave it: the next chunk's candidate entries
-    if (threadIdx.x < kProbe) {
-        u32 rip[kSubs + 1], rop[kSubs + 1];
-        const u64 start = base + threadIdx.x;
-        u32 land = kBadIp;
-        if (start < n) {
-            walk_chunk(T, n, base, static_cast<u32>(start), 0u, rip, rop);
-            land = rip[kSubs];
-        }
-        s_land[threadIdx.x] = (land != kBadIp && land >= end && land < end + kChunk && land < n) ? land : kBadIp;   // (beyond the next chunk: it passes through)
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        CandHandoff* const h = hand + k + 1;
-        u32 cnt = 0;
-        u32 keys[kMaxCand];
-        for (u32 i = 0; i < kProbe && cnt != kWide; ++i) {
-            const u32 v = s_land[i];
-            if (v == kBadIp) continue;
-            bool seen = false;
-#pragma unroll
-            for (u32 c = 0; c < kMaxCand; ++c) seen = seen || (c < cnt && keys[c] == v);
-            if (seen) continue;
-            if (cnt == kMaxCand) { cnt = kWide; break; }
-#pragma unroll
-            for (u32 c = 0; c < kMaxCand; ++c)
-                if (c == cnt) keys[c] = v;
-            ++cnt;
-        }
-#pragma unroll
-        for (u32 c = 0; c < kMaxCand; ++c) {
-            h->key[c] = keys[c];
-            s_next_key[c] = keys[c];
-        }
-        s_next_ncand = cnt;
-        h->ncand = cnt;
-        __hip_atomic_store(&h->ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        // this chunk's own candidates, from the chunk before (which took its ticket earlier and publishes before it waits: no chain)
-        if (k == 0) {
-            s_ncand = 1;
-            s_key[0] = hb;
-        } else {
-            const CandHandoff* const m = hand + k;
-            while (__hip_atomic_load(&m->ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(1);
-            const u32 nc = m->ncand;
-            s_ncand = nc;
-            for (u32 c = 0; c < kMaxCand && nc != kWide && c < nc; ++c) s_key[c] = m->key[c];
-        }
-    }
-    __syncthreads();
-    const u32 nc = s_ncand;
-    CandTable* const t = tables + k;
-    if (threadIdx.x == 0) t->ncand = nc;
-    if (nc != kWide && threadIdx.x < nc) {
-        u32 rip[kSubs + 1], rop[kSubs + 1];
-        const u32 key = s_key[threadIdx.x];
-        walk_chunk(T, n, base, key, 0u, rip, rop);
-        t->key[threadIdx.x] = key;
-        for (u32 sc = 1; sc <= kSubs; ++sc) {
-            t->ip[threadIdx.x][sc - 1] = rip[sc];
-            t->op[threadIdx.x][sc - 1] = rop[sc];
-        }
-        const u32 out = rip[kSubs];
-        u32 nx = out == kBadIp ? kFail : out == n ? kDone : kByPos;
-        if (nx == kByPos && s_next_ncand != kWide)
-            for (u32 c = 0; c < kMaxCand; ++c)
-                if (c < s_next_ncand && s_next_key[c] == out) nx = c;
-        t->nxt[threadIdx.x] = nx;
-    }
+    cand_chunk(T, s_raw, s_land, s_ncand, s_key, s_next_ncand, s_next_key, src, n, hb, k, tables, hand);
 }
 
 // One workgroup: scan; while a landing is pending: give it (and what follows it, up to the rejoin) rows, scan again.
@@ -197,32 +95,17 @@ __global__ __launch_bounds__(256) void k_fragment_starts(const u64* __restrict__
     if (f >= nfrag) return;
     const u64* const entries = *fallback ? looked_back : scanned;
     const u32 target = f * SNP_BLOCK_SIZE;
-    const u64 last = entries[nent - 1];
-    const bool good = static_cast<u32>(last) == n && (static_cast<u32>(last >> 32) & 0x7fffffffu) == expected;
+    const FragStart fs = fragment_start(entries, nent, n, expected, target);
     out_off[f] = target;
     out_cap[f] = expected - target < SNP_BLOCK_SIZE ? expected - target : SNP_BLOCK_SIZE;
-    if (!good) {                              // the fragment decoder then reports "incomplete" and the caller falls back
-        in_off[f] = 0;
-        in_len[f] = 0;
-        skip[f] = 0;
-        return;
-    }
-    u32 lo = 0, hi = nent - 1;                // entries are ordered by output offset; entries[0] has offset 0
-    while (lo < hi) {
-        const u32 mid = (lo + hi + 1) / 2;
-        if ((static_cast<u32>(entries[mid] >> 32) & 0x7fffffffu) <= target) lo = mid;
-        else hi = mid - 1;
-    }
-    const u64 e = entries[lo];
-    const u32 ip = static_cast<u32>(e);
-    in_off[f] = ip;
-    in_len[f] = n - ip;
-    skip[f] = target - (static_cast<u32>(e >> 32) & 0x7fffffffu);
+    in_off[f] = fs.ip;
+    in_len[f] = fs.good ? n - fs.ip : 0u;
+    skip[f] = fs.skip;
 }
 
 }  // namespace
 
-extern "C" u32 snp_tag_index_entries(u32 n, u32 hb) { return ((n - hb + kChunk - 1) / kChunk) * kSubs + 1; }
+extern "C" u32 snp_tag_index_entries(u32 n, u32 hb) { return snp_tag_chunks(n, hb) * kSubs + 1; }
 
 // Workspace layout (all zeroed by the launch): scanned entries | look-back entries | tickets and flag | hand-offs | candidate tables.
 static size_t ws_entries(u32 nent) { return (static_cast<size_t>(nent) * 8 + 63) / 64 * 64; }
@@ -308,7 +191,7 @@ extern "C" hipError_t snp_launch_tag_index_finish(const u8* src, u32 n, u32 hb, 
     return hipGetLastError();
 }
 
-extern "C" int snp_tag_index_look_back_only(u32 n, u32 expected) { return static_cast<u64>(n) * 100 >= static_cast<u64>(expected) * 85; }
+extern "C" int snp_tag_index_look_back_only(u32 n, u32 expected) { return snp_look_back_only(n, expected); }
 
 extern "C" hipError_t snp_launch_tag_index(const u8* src, u32 n, u32 hb, u32 expected, u64* work, u64* in_off, u32* in_len,
                                            u64* out_off, u32* out_cap, u32* skip, hipStream_t stream)

@@ -1,12 +1,14 @@
 // tag_index_device.h -- the device code of the tag index (tag_index.hip) that its single-block kernels and the batched kernels of
-// buffers_decode.hip share: the per-chunk table (build_table) and walk (walk_chunk), the candidate tables and hand-offs, the scan
-// (scan_step / scan_pass) and its fix pass (fix_pass).  How they work together: tag_index.hip's header comment.
+// buffers_decode.hip share: the per-chunk table (build_table) and walk (walk_chunk), the look-back of one chunk (look_back_chunk), the
+// candidate tables and hand-offs and the candidate pass of one chunk (cand_chunk), the scan (scan_step / scan_pass) and its fix pass
+// (fix_pass), the search of one fragment's start (fragment_start).  The kernels of both files are drivers: they own the ticket, the early
+// return on their flag and their LDS, and call these.  How the steps work together: tag_index.hip's header comment.
 #pragma once
-#include "snp_device.h"
+#include "snp_rules.h"
 
 namespace {
 
-constexpr u32 kChunk = 16384;
+constexpr u32 kChunk = SNP_TAG_CHUNK;
 constexpr u32 kThreads = 1024;                    // one workgroup per CU (128 KiB of LDS): sixteen wavefronts hide the LDS latency of the pointer doubling
 constexpr u32 kSub = 4096;
 constexpr u32 kSubs = kChunk / kSub;
@@ -72,13 +74,13 @@ __device__ __forceinline__ void build_table(u64* T, u8* raw, const u8* __restric
     }
 }
 
-// Step 2's walk for one entry point: from (ip, op) through the chunk's sub-chunks; rec_ip / rec_op[sc] = the entry point of sub-chunk sc (sc >= 1)
-// as the look-back records it, [kSubs] = the entry of the next chunk.
-__device__ __forceinline__ void walk_chunk(const u64* T, const u32 n, const u64 base, u32 ip, u32 op, u32* rec_ip, u32* rec_op)
+// Step 2's walk for one entry point: from (ip, op) through the chunk's sub-chunks; rec(sc, ip, op) is given the entry point of sub-chunk sc as
+// the look-back records it (sc = 0: the entry itself), then rec(kSubs, ..) the entry of the next chunk.
+template <class Rec>
+__device__ __forceinline__ void walk_chunk(const u64* T, const u32 n, const u64 base, u32 ip, u32 op, Rec rec)
 {
     for (u32 sc = 0; sc < kSubs; ++sc) {
-        rec_ip[sc] = ip;
-        rec_op[sc] = op;
+        rec(sc, ip, op);
         const u64 sub_end = base + static_cast<u64>(sc + 1) * kSub;
         if (ip == kBadIp || ip >= n || ip >= sub_end) continue;           // finished, irregular, or a literal jumps over this sub-chunk
         const u64 e = T[ip - base];
@@ -88,8 +90,40 @@ __device__ __forceinline__ void walk_chunk(const u64* T, const u32 n, const u64 
         ip = static_cast<u32>(base + nx);
         op = static_cast<u32>(sum);
     }
-    rec_ip[kSubs] = ip;
-    rec_op[kSubs] = op;
+    rec(kSubs, ip, op);
+}
+// (the record as two arrays of kSubs + 1)
+__device__ __forceinline__ void walk_chunk(const u64* T, const u32 n, const u64 base, u32 ip, u32 op, u32* rec_ip, u32* rec_op)
+{
+    walk_chunk(T, n, base, ip, op, [&](u32 sc, u32 at, u32 out) { rec_ip[sc] = at; rec_op[sc] = out; });
+}
+
+// Step 2 for chunk k of a stream (the caller took k from a ticket counter, so chunk k - 1 started earlier): the true entry of the chunk from its
+// neighbour, through its sub-chunks, to the entry of chunk k + 1.  T, raw: the workgroup's LDS, read until the caller's next barrier.
+__device__ __forceinline__ void look_back_chunk(u64* T, u8* raw, const u8* __restrict__ src, const u32 n, const u32 hb, const u32 k, u64* __restrict__ entries)
+{
+    const u64 base = hb + static_cast<u64>(k) * kChunk;               // stream offset of this chunk
+    build_table(T, raw, src, n, base);
+    if (threadIdx.x == 0) {
+        u64 ent;
+        if (k == 0) {
+            ent = kValid | pack(0, hb);                                  // the first tag follows the varint preamble
+        } else {
+            // The hand-off IS this one 8-byte word (valid bit | output offset | stream position): a relaxed agent-scope load
+            // (L2-served) and store are enough -- no payload behind a flag, so no acquire/release and no cache invalidation per
+            // poll (MI355X_MICROARCH.md, hand-off price list: acquire polling costs 2-3x per hop).  Measured: 4.6 -> 0.84 us per hop
+            // (k_tag_index over a 0.29 GiB stream: 86 -> 15.7 ms).
+            while ((ent = __hip_atomic_load(&entries[static_cast<u64>(k) * kSubs], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0)
+                __builtin_amdgcn_s_sleep(1);
+        }
+        // the entry points go to the table as the walk meets them; the next chunk's, which the neighbour spins on, last
+        walk_chunk(T, n, base, static_cast<u32>(ent), static_cast<u32>(ent >> 32) & 0x7fffffffu, [&](u32 sc, u32 ip, u32 op) {
+            const u64 e = kValid | pack(op, ip);                          // (ip: stream offset of a tag start, or n, or kBadIp; op: output bytes before it)
+            if (sc == kSubs) __hip_atomic_store(&entries[static_cast<u64>(k + 1) * kSubs], e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else if (sc) entries[static_cast<u64>(k) * kSubs + sc] = e;
+            else if (k == 0) entries[0] = e;
+        });
+    }
 }
 
 // ---- steps 2a / 2b: candidate entries per chunk, then one serial pass over the candidate tables ------------------------------------------
@@ -113,6 +147,86 @@ struct CandHandoff {                              // chunk k - 1 -> chunk k: the
     u32 ncand;
     u32 key[kMaxCand];
 };
+
+// Step 2a for chunk k of a stream (k from a ticket counter, as above): the next chunk's candidates are published BEFORE this chunk's own are
+// waited for, so there is no chain.  T .. s_next_key: the workgroup's LDS, read until the caller's next barrier.
+__device__ __forceinline__ void cand_chunk(u64* T, u8* raw, u32* s_land, u32& s_ncand, u32* s_key, u32& s_next_ncand, u32* s_next_key,
+                                           const u8* __restrict__ src, const u32 n, const u32 hb, const u32 k, CandTable* __restrict__ tables,
+                                           CandHandoff* __restrict__ hand)
+{
+    const u64 base = hb + static_cast<u64>(k) * kChunk;
+    const u64 end = base + kChunk;
+    build_table(T, raw, src, n, base);
+    // where the walks that enter at the chunk's first bytes leave it: the next chunk's candidate entries
+    if (threadIdx.x < kProbe) {
+        u32 rip[kSubs + 1], rop[kSubs + 1];
+        const u64 start = base + threadIdx.x;
+        u32 land = kBadIp;
+        if (start < n) {
+            walk_chunk(T, n, base, static_cast<u32>(start), 0u, rip, rop);
+            land = rip[kSubs];
+        }
+        s_land[threadIdx.x] = (land != kBadIp && land >= end && land < end + kChunk && land < n) ? land : kBadIp;   // (beyond the next chunk: it passes through)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        CandHandoff* const h = hand + k + 1;
+        u32 cnt = 0;
+        u32 keys[kMaxCand];
+        for (u32 i = 0; i < kProbe && cnt != kWide; ++i) {
+            const u32 v = s_land[i];
+            if (v == kBadIp) continue;
+            bool seen = false;
+#pragma unroll
+            for (u32 c = 0; c < kMaxCand; ++c) seen = seen || (c < cnt && keys[c] == v);
+            if (seen) continue;
+            if (cnt == kMaxCand) { cnt = kWide; break; }
+#pragma unroll
+            for (u32 c = 0; c < kMaxCand; ++c)
+                if (c == cnt) keys[c] = v;
+            ++cnt;
+        }
+#pragma unroll
+        for (u32 c = 0; c < kMaxCand; ++c) {
+            h->key[c] = keys[c];
+            s_next_key[c] = keys[c];
+        }
+        s_next_ncand = cnt;
+        h->ncand = cnt;
+        __hip_atomic_store(&h->ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        // this chunk's own candidates, from the chunk before (which took its ticket earlier and publishes before it waits: no chain)
+        if (k == 0) {
+            s_ncand = 1;
+            s_key[0] = hb;
+        } else {
+            const CandHandoff* const m = hand + k;
+            while (__hip_atomic_load(&m->ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(1);
+            const u32 nc = m->ncand;
+            s_ncand = nc;
+            for (u32 c = 0; c < kMaxCand && nc != kWide && c < nc; ++c) s_key[c] = m->key[c];
+        }
+    }
+    __syncthreads();
+    const u32 nc = s_ncand;
+    CandTable* const t = tables + k;
+    if (threadIdx.x == 0) t->ncand = nc;
+    if (nc != kWide && threadIdx.x < nc) {
+        u32 rip[kSubs + 1], rop[kSubs + 1];
+        const u32 key = s_key[threadIdx.x];
+        walk_chunk(T, n, base, key, 0u, rip, rop);
+        t->key[threadIdx.x] = key;
+        for (u32 sc = 1; sc <= kSubs; ++sc) {
+            t->ip[threadIdx.x][sc - 1] = rip[sc];
+            t->op[threadIdx.x][sc - 1] = rop[sc];
+        }
+        const u32 out = rip[kSubs];
+        u32 nx = out == kBadIp ? kFail : out == n ? kDone : kByPos;
+        if (nx == kByPos && s_next_ncand != kWide)
+            for (u32 c = 0; c < kMaxCand; ++c)
+                if (c < s_next_ncand && s_next_key[c] == out) nx = c;
+        t->nxt[threadIdx.x] = nx;
+    }
+}
 
 // ---- step 2b: the scan --------------------------------------------------------------------------------------------------------------------
 // The state between two chunks: a ROW of the next chunk's table, a POSITION further on (looked up when its chunk comes), the END of the
@@ -336,5 +450,30 @@ __device__ __forceinline__ void fix_pass(const u8* __restrict__ src, u32 n, u32 
     }
     if (threadIdx.x == 0) ctl->pending = 0;
     __syncthreads();
+}
+
+// ---- the fragment table ---------------------------------------------------------------------------------------------------------------------------
+// Where the decoder of the fragment whose first output byte is `target` starts: the last entry at or before it (ip: its stream position, skip:
+// the output bytes between it and `target`).  good = false: the table is irregular (it does not end at (n, expected)) -- the fragment decoder
+// is then given nothing to read, reports "incomplete", and the caller falls back.
+struct FragStart {
+    bool good;
+    u32 ip, skip;
+};
+__device__ __forceinline__ FragStart fragment_start(const u64* __restrict__ entries, const u32 nent, const u32 n, const u32 expected, const u32 target)
+{
+    const u64 last = entries[nent - 1];
+    FragStart r{static_cast<u32>(last) == n && (static_cast<u32>(last >> 32) & 0x7fffffffu) == expected, 0, 0};
+    if (!r.good) return r;
+    u32 lo = 0, hi = nent - 1;                // entries are ordered by output offset; entries[0] has offset 0
+    while (lo < hi) {
+        const u32 mid = (lo + hi + 1) / 2;
+        if ((static_cast<u32>(entries[mid] >> 32) & 0x7fffffffu) <= target) lo = mid;
+        else hi = mid - 1;
+    }
+    const u64 e = entries[lo];
+    r.ip = static_cast<u32>(e);
+    r.skip = target - (static_cast<u32>(e >> 32) & 0x7fffffffu);
+    return r;
 }
 }  // namespace

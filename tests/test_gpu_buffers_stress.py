@@ -1,5 +1,5 @@
 """snp_decompress_buffers_batch at scale, on corrupt streams and under every decode option: the batched tag index (k_bd_tag_cand, k_bd_tag_scan,
-k_bd_tag_look_back -- their own copies of the per-chunk code of tag_index.hip), the makespan rule, admission by max_fragments, the plan scans
+k_bd_tag_look_back -- drivers of the per-chunk code that tag_index.hip's kernels run), the makespan rule, admission by max_fragments, the plan scans
 past 256 tiles (and the two scans of snp_compress_buffers_batch), the fallback list.  References: the oracle for bytes and statuses,
 snp_decompress_batch on the same arguments, the NumPy plan() of tests/test_decompress_buffers_model.py for d_result[0..2], and the
 single-block path (snp_try_decompress) for each stream's look-back decision, d_result[3].  Needs an MI355X."""
