@@ -158,6 +158,10 @@ _EXTENSIONS = {
         "snp_decompress_layout_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
         "snp_frame_decode_layout_workspace": (_u64, [_u32, _u32]),
         "snp_frame_decode_layout_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch range decode of framed streams: a window of every stream
+    "frame_range": ("libsnappier_hip_frame_range.so", "snappier_hip_frame_range.h", {
+        "snp_frame_decode_range_workspace": (_u64, [_u32, _u32, _u32, _u64]),
+        "snp_frame_decode_range_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -196,6 +200,7 @@ BUFFERS_PATH = _extension_path("buffers")
 BUFFERS_DECOMPRESS_PATH = _extension_path("buffers_decompress")
 FRAME_BUFFERS_PATH = _extension_path("frame_buffers")
 LAYOUT_PATH = _extension_path("layout")
+FRAME_RANGE_PATH = _extension_path("frame_range")
 
 
 def buffers_lib() -> C.CDLL:
@@ -218,6 +223,11 @@ def layout_lib() -> C.CDLL:
     return _extension("layout")
 
 
+def frame_range_lib() -> C.CDLL:
+    """libsnappier_hip_frame_range.so (include/snappier_hip_frame_range.h)."""
+    return _extension("frame_range")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -232,6 +242,10 @@ def frame_buffers_declared_symbols() -> list[str]:
 
 def layout_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("layout"))
+
+
+def frame_range_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_range"))
 
 
 def status_string(st: int) -> str:

@@ -334,6 +334,80 @@ class BlockCodec:
         out_len, status, _ = self.frame_decode_buffers(framed, in_off, in_len, out, out_off, out_cap, max_chunks=min(chunks, 0xFFFFFFFF), max_spans=spans)
         return out[:need], out_off, out_len, status
 
+    def frame_decode_range_buffers(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, range_off: torch.Tensor,
+                                   range_len: torch.Tensor, out: torch.Tensor, out_off: torch.Tensor, out_cap: torch.Tensor,
+                                   max_chunks: int | None = None, max_spans: int | None = None, edge_cap: int | None = None,
+                                   work: torch.Tensor | None = None):
+        """A window of decoded bytes out of every framed stream (snp_frame_decode_range_batch, libsnappier_hip_frame_range.so):
+        -> (out_len, status, result).
+
+        Stream b is framed[in_off[b] .. +in_len[b]); bytes [range_off[b], range_off[b] + range_len[b]) of what it decodes to, clipped to its
+        length like a read, go to out[out_off[b] .. +out_cap[b]) (int64 tensors, read as unsigned).  Only the chunks that meet the window are
+        decoded and CRC-verified; a stream whose header walk ends in an error is not OK wherever its window lies (include/snappier_hip_frame_range.h).
+        result is the 6-element int64 d_result: [0] = interior chunk slots needed, [1] = sum of out_len over the OK streams, [2] = span slots
+        needed, [3] = spans the resolver walked on the spot, [4] = edge scratch bytes needed, [5] = chunks selected.
+        Default max_spans: EXACT (sum of ceil(in_len / 2^20)), ONE synchronising read-back.  Default max_chunks and edge_cap: a first call with
+        both 0 (it walks every stream and decodes nothing), then a synchronising read of its d_result[0] and [4].  A caller that passes
+        max_chunks, max_spans, edge_cap and work enqueues only."""
+        self._bind()
+        ns = in_len.numel()
+        RL = N.frame_range_lib()
+        if max_spans is None:
+            n = in_len.to(torch.int64)
+            max_spans = int(((n + (1 << 20) - 1) >> 20).sum().item()) if ns else 0
+        framed, out = self._readable(framed, ns), self._readable(out, ns)
+        out_len = torch.empty(ns, dtype=torch.int64, device=self.device)
+        status = torch.empty(ns, dtype=torch.int32, device=self.device)
+        result = torch.empty(6, dtype=torch.int64, device=self.device)
+
+        def call(mc: int, ec: int, w: torch.Tensor | None):
+            w = self._work("frame_decode_range_buffers", w, RL.snp_frame_decode_range_workspace, ns, mc, max_spans, ec)
+            st = RL.snp_frame_decode_range_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(range_off), _p(range_len), mc,
+                                                 max_spans, ec, _p(out), _p(out_off), _p(out_cap), _p(out_len), _p(status), _p(w), _p(result))
+            raise_for_status(st, self.ctx.handle)
+
+        if max_chunks is None or edge_cap is None:
+            call(0, 0, None)
+            need = result.tolist()
+            max_chunks = min(need[0], 0xFFFFFFFF) if max_chunks is None else max_chunks
+            edge_cap = need[4] if edge_cap is None else edge_cap
+        call(max_chunks, edge_cap, work)
+        return out_len, status, result
+
+    def frame_read_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, range_off: torch.Tensor,
+                             range_len: torch.Tensor, align: int = 1, max_bytes: int | None = None):
+        """Read a window of every framed stream given nothing but the framed tensor, its table and the windows: -> (out, out_off, out_len, status).
+
+        Windows are clipped to the stream, so range_len[b] bounds what stream b delivers; so does 22 x in_len[b] (no chunk decodes to more:
+        frame_hop's expansion rule).  Stream b's slot is the smaller of the two rounded up to `align`, out_off[b] the sum of the slots before
+        it.  ONE sizing call (max_chunks = edge_cap = 0: it walks and decodes nothing) with ONE synchronising read of its result and of the
+        arena size (ValueError if that is above max_bytes), then one decode.  max_spans is bounded without a read-back by nstreams + framed
+        bytes / 2^20; only a table whose ranges overlap can need more, and then the sizing call is made again with result[2]."""
+        ns = in_len.numel()
+        empty = torch.empty(0, dtype=torch.uint8, device=self.device)
+        if ns == 0:
+            z = torch.empty(0, dtype=torch.int64, device=self.device)
+            return empty, z, z.clone(), torch.empty(0, dtype=torch.int32, device=self.device)
+        rl = range_len.to(torch.int64)
+        bound = in_len.to(torch.int64) * 22
+        out_cap = torch.where((rl < 0) | (rl > bound), bound, rl)            # (a negative int64 is a length of 2^63 or more)
+        slot = (out_cap + (align - 1)) // align * align
+        ends = torch.cumsum(slot, 0)
+        out_off = ends - slot
+        spans = min(ns + (framed.numel() >> 20), 0xFFFFFFFF)
+        _, _, result = self.frame_decode_range_buffers(framed, in_off, in_len, range_off, range_len, empty, out_off, out_cap, 0, spans, 0)
+        need = torch.cat([result, ends[-1:]]).tolist()
+        if need[2] > spans:
+            spans = need[2]
+            _, _, result = self.frame_decode_range_buffers(framed, in_off, in_len, range_off, range_len, empty, out_off, out_cap, 0, spans, 0)
+            need = result.tolist() + need[-1:]
+        if max_bytes is not None and need[-1] > max_bytes:
+            raise ValueError(f"frame_read_to_memory: the windows take {need[-1]} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need[-1], 1), dtype=torch.uint8, device=self.device)
+        out_len, status, _ = self.frame_decode_range_buffers(framed, in_off, in_len, range_off, range_len, out, out_off, out_cap,
+                                                             max_chunks=min(need[0], 0xFFFFFFFF), max_spans=spans, edge_cap=need[4])
+        return out[:need[-1]], out_off, out_len, status
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()

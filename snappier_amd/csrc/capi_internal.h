@@ -5,7 +5,7 @@
 //     capi_batch.hip   launch policy of the device-pointer batch entry points (which kernel for which batch), snp_*_batch
 //     capi_host.hip    the host-pointer calls: snp_try_compress / snp_try_decompress (+ segments), snp_crc32c
 //     capi_frame.hip   framing orchestration: snp_frame_encode* / snp_frame_decode*
-// The batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip: one file and one header under include/ each)
+// The batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip, frame_range.hip: one file and one header under include/ each)
 // are linked against libsnappier_hip.so and drive its contexts through this header; what they share among themselves is in work_carver.h,
 // scan_tiles.h and frame_walk_device.h.
 // No codec arithmetic happens on the host: every byte of compress / decompress / CRC work is done by the gfx950 kernels in compress_lanes.hip,

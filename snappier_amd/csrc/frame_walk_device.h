@@ -1,7 +1,7 @@
 // frame_walk_device.h -- the span walk over MANY framed streams, end to end: the span tables and the per-stream record with their place in a
 // workspace (carve_span_walk), the piece scan that gives every stream its first span slot (launch_span_scan), walk A (k_fd_candidates) and walk B
-// (k_fd_resolve) with their launch (launch_span_walk).  Shared by the batch decode (frame_buffers.hip, snp_frame_decode_buffers_batch) and the
-// decode layout (layout.hip, snp_frame_decode_layout_batch); the resolver takes out_cap == nullptr as "no bound" (the layout call asks for the
+// (k_fd_resolve) with their launch (launch_span_walk).  Shared by the batch decode (frame_buffers.hip, snp_frame_decode_buffers_batch), the
+// decode layout (layout.hip, snp_frame_decode_layout_batch) and the range decode (frame_range.hip, snp_frame_decode_range_batch); the resolver takes out_cap == nullptr as "no bound" (the layout call asks for the
 // totals, it has no capacities yet).
 #pragma once
 #include "scan_tiles.h"
