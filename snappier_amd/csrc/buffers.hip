@@ -79,8 +79,8 @@ __global__ __launch_bounds__(256) void k_buffers_sizes(const u32* __restrict__ i
         status[b] = st;
         ok_len = len;
     }
-    for (u32 d = 32; d >= 1; d >>= 1) ok_len += __shfl_xor(ok_len, d, 64);
-    if ((threadIdx.x & 63u) == 0 && ok_len) atomicAdd(reinterpret_cast<unsigned long long*>(result + 1), static_cast<unsigned long long>(ok_len));
+    ok_len = wave_sum(ok_len);
+    if ((threadIdx.x & 63u) == 0 && ok_len) atomic_add64(result + 1, ok_len);
 }
 
 // One workgroup per fragment slot: the staged fragment to its place in its buffer's block.

@@ -1,7 +1,9 @@
 // capi_frame.hip -- the framing format end to end (SnappyStreamCompressor.cs:18-21,166-261; SnappyStreamDecompressor.cs:38-208): orchestration of
 // compress + masked CRC + raw-vs-compressed decision + scan + emit on the way in, header walk + decode + CRC verify on the way out.  The kernels are in
-// framing.hip, frame_scan.hip, crc32c.hip and the codec files; this file only sequences them and moves host buffers.
+// framing.hip, frame_scan.hip, crc32c.hip and the codec files; this file only sequences them and moves host buffers.  The host walk over a stream's
+// chunk headers (scan_chunks) is a loop over frame_hop (frame_hop_device.h), the hop the device walks take.
 #include "capi_internal.h"
+#include "frame_hop_device.h"
 
 // workspace layout for snp_frame_encode_device (all sub-arrays 16-byte aligned)
 struct FrameWork {
@@ -57,6 +59,34 @@ snp_status snp_frame_encode_impl(snp_ctx* c, const uint8_t* d_in, const uint8_t*
     return ok ? SNP_OK : SNP_ERR_DEVICE;
 }
 
+bool snp_ctx::decode_chunks(const u8* d_in, const ChunkRows& r, u32 n, u8* d_out)
+{
+    return launch_decompress(d_in, r.body_off, r.body_len, n, d_out, r.out_off, r.out_cap, r.out_len, r.status, r.type) &&
+           check(snp_launch_crc32c(d_out, r.out_off, r.out_len, n, 1 | crc_bits(), nullptr, r.crc, r.status, stream), "frame crc verify");
+}
+
+// The chunk table of the one-stream calls, packed (no padding between the arrays; the order keeps every array aligned when base is 8-byte
+// aligned): body_off, out_off (u64) ; body_len, crc, out_cap, out_len (u32) ; status (i32) ; type (u8).  snp_frame_decode_workspace promises
+// this size, so the table is not carved by WorkCarver like those of the batch calls.
+struct PackedRows {
+    ChunkRows r;
+    u64 bytes;
+};
+static PackedRows packed_chunk_rows(void* base, u64 n)
+{
+    u8* p = static_cast<u8*>(base);
+    PackedRows w{};
+    auto take = [&](u64 bytes) { u8* piece = p ? p + w.bytes : nullptr; w.bytes += bytes; return piece; };
+    w.r.body_off = reinterpret_cast<u64*>(take(n * 8));
+    w.r.out_off = reinterpret_cast<u64*>(take(n * 8));
+    w.r.body_len = reinterpret_cast<u32*>(take(n * 4));
+    w.r.crc = reinterpret_cast<u32*>(take(n * 4));
+    w.r.out_cap = reinterpret_cast<u32*>(take(n * 4));
+    w.r.out_len = reinterpret_cast<u32*>(take(n * 4));
+    w.r.status = reinterpret_cast<i32*>(take(n * 4));
+    w.r.type = take(n);
+    return w;
+}
 
 extern "C" {
 
@@ -83,20 +113,23 @@ snp_status snp_frame_decode_chunks_device(snp_ctx* c, const uint8_t* d_in, const
         return SNP_ERR_BAD_ARG;
     DevGuard dg(c);
     if (!dg.ok) return SNP_ERR_DEVICE;
-    hipStream_t s = c->stream;
-    bool ok = c->launch_decompress(d_in, body_off, body_len, nchunks, d_out, out_off, out_cap, out_len, status, chunk_type);
-    // CRC over the produced bytes, compared with the chunk's stored masked CRC  (SnappyStreamDecompressor.cs:117-131)
-    ok = ok && c->check(snp_launch_crc32c(d_out, out_off, out_len, nchunks, 1 | c->crc_bits(), nullptr, chunk_crc, status, s),
-                        "frame crc verify");
-    return ok ? SNP_OK : SNP_ERR_DEVICE;
+    ChunkRows r{};                                                      // (the caller's table: decode_chunks writes out_len and status only)
+    r.type = const_cast<u8*>(chunk_type);
+    r.body_off = const_cast<u64*>(body_off);
+    r.body_len = const_cast<u32*>(body_len);
+    r.crc = const_cast<u32*>(chunk_crc);
+    r.out_off = const_cast<u64*>(out_off);
+    r.out_cap = const_cast<u32*>(out_cap);
+    r.out_len = out_len;
+    r.status = status;
+    return c->decode_chunks(d_in, r, nchunks, d_out) ? SNP_OK : SNP_ERR_DEVICE;
 }
 
 // ---- framed stream without a chunk table: header walk on the device --------------------------------
-// workspace: 64-byte header {total, tail status, chunks} ; body_off, out_off (u64) ; body_len, crc, out_cap, out_len (u32) ;
-// status (i32) ; type (u8)
+// workspace: 64-byte header {total, tail status, chunks} ; the packed chunk table ; 16 bytes
 uint64_t snp_frame_decode_workspace(uint32_t max_chunks)
 {
-    return 64 + snp_align_up(static_cast<u64>(max_chunks) * (8 * 2 + 4 * 5 + 1), 16) + 16;
+    return 64 + snp_align_up(packed_chunk_rows(nullptr, max_chunks).bytes, 16) + 16;
 }
 
 snp_status snp_frame_decode_device(snp_ctx* c, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap,
@@ -107,29 +140,20 @@ snp_status snp_frame_decode_device(snp_ctx* c, const uint8_t* d_in, uint64_t n, 
     if (!dg.ok) return SNP_ERR_DEVICE;
     hipStream_t s = c->stream;
     u64* hdr = static_cast<u64*>(d_work);
-    u64* body_off = hdr + 8;
-    u64* out_off = body_off + max_chunks;
-    u32* body_len = reinterpret_cast<u32*>(out_off + max_chunks);
-    u32* crc = body_len + max_chunks;
-    u32* out_cap = crc + max_chunks;
-    u32* out_len = out_cap + max_chunks;
-    i32* status = reinterpret_cast<i32*>(out_len + max_chunks);
-    u8* type = reinterpret_cast<u8*>(status + max_chunks);
+    const ChunkRows r = packed_chunk_rows(hdr + 8, max_chunks).r;
     bool ok;
     if (c->frame_scan == 1) {
-        ok = c->check(snp_launch_frame_scan(d_in, n, cap, max_chunks, type, body_off, body_len, crc, out_off, out_cap, hdr, s), "frame scan");
+        ok = c->check(snp_launch_frame_scan(d_in, n, cap, max_chunks, r, hdr, s), "frame scan");
     } else {
         // per-span candidate tables live in context scratch (a few MB per 10 GiB of stream; grows on first use only)
         if (!c->ensure(c->scan, snp_frame_scan_workspace(n), "hipMalloc(frame scan)")) return SNP_ERR_DEVICE;
-        ok = c->check(snp_launch_frame_scan_spans(d_in, n, cap, max_chunks, type, body_off, body_len, crc, out_off, out_cap, hdr,
-                                                  c->scan.p, s), "frame scan (spans)");
+        ok = c->check(snp_launch_frame_scan_spans(d_in, n, cap, max_chunks, r, hdr, c->scan.p, s), "frame scan (spans)");
     }
     if (ok && max_chunks && n) {                     // n == 0: no chunk, nothing to launch
-        const snp_status st = snp_frame_decode_chunks_device(c, d_in, type, body_off, body_len, crc, max_chunks, d_out, out_off,
-                                                             out_cap, out_len, status);
-        if (st != SNP_OK) return st;
+        if (!d_out) return SNP_ERR_BAD_ARG;          // (as snp_frame_decode_chunks_device: a table to decode needs an output, whatever cap is)
+        if (!c->decode_chunks(d_in, r, max_chunks, d_out)) return SNP_ERR_DEVICE;
     }
-    ok = ok && c->check(snp_launch_frame_result(status, hdr, d_result, s), "frame result");
+    ok = ok && c->check(snp_launch_frame_result(r.status, hdr, d_result, s), "frame result");
     return ok ? SNP_OK : SNP_ERR_DEVICE;
 }
 
@@ -173,37 +197,20 @@ struct ChunkScan {
 };
 static void scan_chunks(const u8* in, size_t n, ChunkScan& cs)
 {
-    size_t ip = 0;
-    while (ip < n) {
-        if (n - ip < 4) { cs.tail = SNP_ERR_TRUNCATED_STREAM; return; }
-        const u32 type = in[ip];
-        const u32 size = in[ip + 1] | (in[ip + 2] << 8) | (static_cast<u32>(in[ip + 3]) << 16);   // :64-65
-        ip += 4;
-        if (n - ip < size) { cs.tail = SNP_ERR_TRUNCATED_STREAM; return; }
-        if (type == 0x00 || type == 0x01) {
-            if (size < 4) { cs.tail = SNP_ERR_TRUNCATED_STREAM; return; }
-            u32 crc;
-            memcpy(&crc, in + ip, 4);                                    // ReadChunkCrc  :260-289
-            u32 dec = size - 4, hb = 0;
-            if (type == 0x00 && snp_get_uncompressed_length(in + ip + 4, size - 4, &dec, &hb) != SNP_OK) {
-                cs.tail = SNP_ERR_BAD_LENGTH;
-                return;
-            }
-            if (dec > 0x7fffffffu) { cs.tail = SNP_ERR_BAD_LENGTH; return; }
-            // a chunk that declares more than its body can possibly produce (snp_rules.h) is "Incomplete Snappy block."
-            if (type == 0x00 && dec > snp_max_expansion(size - 4 - hb)) { cs.tail = SNP_ERR_INCOMPLETE; return; }
-            cs.type.push_back(static_cast<u8>(type));
-            cs.body_off.push_back(ip + 4);
-            cs.body_len.push_back(size - 4);
-            cs.crc.push_back(crc);
+    for (u64 ip = 0;;) {
+        const Hop h = frame_hop(in, n, ip);
+        if (h.kind == HOP_END) return;
+        if (h.kind == HOP_ERR) { cs.tail = static_cast<snp_status>(h.err); return; }
+        if (h.kind == HOP_DATA) {
+            cs.type.push_back(static_cast<u8>(h.type));
+            cs.body_off.push_back(ip + SNP_CHUNK_HEADER_LEN);
+            cs.body_len.push_back(h.body_len);
+            cs.crc.push_back(h.crc);
             cs.out_off.push_back(cs.total);
-            cs.out_cap.push_back(dec);
-            cs.total += dec;
-        } else if (type < 0x80) {                                        // :182-185
-            cs.tail = SNP_ERR_CHUNK_TYPE;
-            return;
-        }                                                                // 0x80..0xff skipped unvalidated  :187-196
-        ip += size;
+            cs.out_cap.push_back(h.dec);
+            cs.total += h.dec;
+        }
+        ip = h.next;
     }
 }
 
@@ -228,33 +235,20 @@ snp_status snp_frame_decode(snp_ctx* c, const uint8_t* in, size_t n, uint8_t* ou
     if (cs.total > cap) return SNP_ERR_OUTPUT_TOO_SMALL;
     if (nc == 0) return cs.tail;
     hipStream_t s = c->stream;
-    // meta: body_off, out_off (u64) ; body_len, crc, out_cap, out_len (u32) ; status (i32) ; type (u8)
-    const u64 meta_bytes = static_cast<u64>(nc) * (8 * 2 + 4 * 5 + 1) + 64;
     if (!c->ensure(c->in, n + 16, "hipMalloc(in)") || !c->ensure(c->out, cs.total + 16, "hipMalloc(out)") ||
-        !c->ensure(c->meta, meta_bytes, "hipMalloc(meta)"))
+        !c->ensure(c->meta, packed_chunk_rows(nullptr, nc).bytes + 64, "hipMalloc(meta)"))
         return SNP_ERR_DEVICE;
-    u64* d_body_off = static_cast<u64*>(c->meta.p);
-    u64* d_out_off = d_body_off + nc;
-    u32* d_body_len = reinterpret_cast<u32*>(d_out_off + nc);
-    u32* d_crc = d_body_len + nc;
-    u32* d_out_cap = d_crc + nc;
-    u32* d_out_len = d_out_cap + nc;
-    i32* d_status = reinterpret_cast<i32*>(d_out_len + nc);
-    u8* d_type = reinterpret_cast<u8*>(d_status + nc);
+    const ChunkRows r = packed_chunk_rows(c->meta.p, nc).r;
     bool ok = c->h2d(c->in.p, in, n, "H2D input");
-    ok = ok && c->check(hipMemcpyAsync(d_body_off, cs.body_off.data(), nc * 8ull, hipMemcpyHostToDevice, s), "H2D meta");
-    ok = ok && c->check(hipMemcpyAsync(d_out_off, cs.out_off.data(), nc * 8ull, hipMemcpyHostToDevice, s), "H2D meta");
-    ok = ok && c->check(hipMemcpyAsync(d_body_len, cs.body_len.data(), nc * 4ull, hipMemcpyHostToDevice, s), "H2D meta");
-    ok = ok && c->check(hipMemcpyAsync(d_crc, cs.crc.data(), nc * 4ull, hipMemcpyHostToDevice, s), "H2D meta");
-    ok = ok && c->check(hipMemcpyAsync(d_out_cap, cs.out_cap.data(), nc * 4ull, hipMemcpyHostToDevice, s), "H2D meta");
-    ok = ok && c->check(hipMemcpyAsync(d_type, cs.type.data(), nc, hipMemcpyHostToDevice, s), "H2D meta");
-    if (!ok) return SNP_ERR_DEVICE;
-    snp_status st = snp_frame_decode_chunks_device(c, static_cast<const u8*>(c->in.p), d_type, d_body_off, d_body_len,
-                                                   d_crc, nc, static_cast<u8*>(c->out.p), d_out_off, d_out_cap, d_out_len,
-                                                   d_status);
-    if (st != SNP_OK) return st;
+    ok = ok && c->check(hipMemcpyAsync(r.body_off, cs.body_off.data(), nc * 8ull, hipMemcpyHostToDevice, s), "H2D meta");
+    ok = ok && c->check(hipMemcpyAsync(r.out_off, cs.out_off.data(), nc * 8ull, hipMemcpyHostToDevice, s), "H2D meta");
+    ok = ok && c->check(hipMemcpyAsync(r.body_len, cs.body_len.data(), nc * 4ull, hipMemcpyHostToDevice, s), "H2D meta");
+    ok = ok && c->check(hipMemcpyAsync(r.crc, cs.crc.data(), nc * 4ull, hipMemcpyHostToDevice, s), "H2D meta");
+    ok = ok && c->check(hipMemcpyAsync(r.out_cap, cs.out_cap.data(), nc * 4ull, hipMemcpyHostToDevice, s), "H2D meta");
+    ok = ok && c->check(hipMemcpyAsync(r.type, cs.type.data(), nc, hipMemcpyHostToDevice, s), "H2D meta");
+    if (!ok || !c->decode_chunks(static_cast<const u8*>(c->in.p), r, nc, static_cast<u8*>(c->out.p))) return SNP_ERR_DEVICE;
     std::vector<i32> status(nc);
-    ok = c->check(hipMemcpyAsync(status.data(), d_status, nc * 4ull, hipMemcpyDeviceToHost, s), "D2H status") &&
+    ok = c->check(hipMemcpyAsync(status.data(), r.status, nc * 4ull, hipMemcpyDeviceToHost, s), "D2H status") &&
          c->check(hipStreamSynchronize(s), "sync");
     if (!ok) return SNP_ERR_DEVICE;
     for (u32 i = 0; i < nc; ++i)                                          // first failing chunk in stream order wins,

@@ -4,10 +4,11 @@
 //     capi_pool.hip    one hash-table workspace per DEVICE (TablePool), its placement search (piece_search.h), borrow / return
 //     capi_batch.hip   launch policy of the device-pointer batch entry points (which kernel for which batch), snp_*_batch
 //     capi_host.hip    the host-pointer calls: snp_try_compress / snp_try_decompress (+ segments), snp_crc32c
-//     capi_frame.hip   framing orchestration: snp_frame_encode* / snp_frame_decode*
+//     capi_frame.hip   framing orchestration: snp_frame_encode* / snp_frame_decode*, the host header walk, snp_ctx::decode_chunks
 // The batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip, frame_range.hip: one file and one header under include/ each)
 // are linked against libsnappier_hip.so and drive its contexts through this header; what they share among themselves is in work_carver.h,
-// scan_tiles.h and frame_walk_device.h.
+// scan_tiles.h, frame_hop_device.h (one hop of a framed stream's header walk, the per-span bodies, the span and chunk tables: shared with framing.hip,
+// frame_scan.hip and capi_frame.hip) and frame_walk_device.h (the span walk over many streams).
 // No codec arithmetic happens on the host: every byte of compress / decompress / CRC work is done by the gfx950 kernels in compress_lanes.hip,
 // compress_win.hip, decode_chains.hip, decompress.hip, decompress_small.hip, tag_index.hip, crc32c.hip, framing.hip, frame_scan.hip.
 // There is no CPU fallback -- without a HIP device snp_ctx_create fails with SNP_ERR_DEVICE.
@@ -26,6 +27,16 @@
 #include <vector>
 
 #include "snp_rules.h"
+
+// The chunk table of a framed decode, structure of arrays over n rows: what the header walks write (frame_hop_device.h) and the decoder and the
+// CRC verify read (snp_ctx::decode_chunks).  tag: the row's stream in the batch and range tables (`owner`), its edge slot in the range call's edge
+// table (`src`), kNone for an empty row; the one-stream table has none (nullptr).
+struct ChunkRows {
+    u8* type;
+    u64 *body_off, *out_off;
+    u32 *body_len, *crc, *out_cap, *out_len, *tag;
+    i32* status;
+};
 
 extern "C" {
 hipError_t snp_launch_decompress(const u8*, const u64*, const u32*, u32, u8*, const u64*, const u32*, u32*, i32*,
@@ -58,10 +69,10 @@ hipError_t snp_launch_gather(const u8*, const u64*, const u32*, u8*, const u64*,
 hipError_t snp_launch_frame_chunks(u64, u32, u64, u64*, u32*, u64*, hipStream_t);
 hipError_t snp_launch_frame_plan(const u32*, const u32*, u32, u8*, u32*, u64*, u64*, hipStream_t);
 hipError_t snp_launch_frame_header_only(u8*, u64*, hipStream_t);
-hipError_t snp_launch_frame_scan(const u8*, u64, u64, u32, u8*, u64*, u32*, u32*, u64*, u32*, u64*, hipStream_t);
+hipError_t snp_launch_frame_scan(const u8*, u64, u64, u32, const ChunkRows&, u64*, hipStream_t);
 hipError_t snp_launch_frame_result(const i32*, const u64*, u64*, hipStream_t);
 size_t snp_frame_scan_workspace(u64);
-hipError_t snp_launch_frame_scan_spans(const u8*, u64, u64, u32, u8*, u64*, u32*, u32*, u64*, u32*, u64*, void*, hipStream_t);
+hipError_t snp_launch_frame_scan_spans(const u8*, u64, u64, u32, const ChunkRows&, u64*, void*, hipStream_t);
 hipError_t snp_launch_frame_emit(const u8*, const u64*, const u8*, const u64*, const u8*, const u32*, const u32*,
                                  const u64*, u8*, u64, u32, hipStream_t);
 }
@@ -165,6 +176,9 @@ struct snp_ctx {
                            const u32* out_cap, u32* out_len, i32* status, const u8* chunk_type);
     bool launch_compress(const u8* d_in, const u64* in_off, const u32* in_len, u32 nblocks, u8* d_out, const u64* out_off,
                          u32* out_len, i32* status, int emit_varint);
+    // capi_frame.hip: launch_decompress over the n rows of a chunk table, then the CRC of what each row produced against its stored masked CRC
+    // (SnappyStreamDecompressor.cs:117-131); r.status holds the first of the two that failed
+    bool decode_chunks(const u8* d_in, const ChunkRows& r, u32 n, u8* d_out);
     u32* hint = nullptr;                                 // pinned: the previous batch's list length
     hipEvent_t hint_ev = nullptr;
     bool hint_pending = false, hint_mostly_large = false, hint_from_prepass = false, hint_seen = false;

@@ -21,7 +21,7 @@
 //   scan      chunks listed per stream -> each stream's first chunk slot (d_result[0]); a stream whose chunks do not fit is not decoded
 //   C         one wavefront per span slot: the rows of the span's chunks at their global slots, body and output offsets absolute; one thread per
 //             slot pads every other slot with an empty raw chunk and the CRC of nothing
-//   decode    snp_ctx::launch_decompress(chunk_type) and the verifying snp_launch_crc32c over all max_chunks slots
+//   decode    snp_ctx::decode_chunks over all max_chunks slots: launch_decompress(chunk_type) and the verifying snp_launch_crc32c
 //   verdict   one thread per failing slot: atomicMin of its slot into its stream's word; one thread per stream: the first failing chunk, else
 //             the walk's tail error, else OK (k_frame_result's precedence) -> status, out_len, d_result[1]
 // Nothing here allocates, reads back or synchronises: both calls are capturable like the other _batch entry points.
@@ -100,8 +100,8 @@ __global__ __launch_bounds__(256) void k_fe_sizes(u32 nb, const u64* __restrict_
         status[b] = st;
         ok_len = len;
     }
-    for (u32 d = 32; d >= 1; d >>= 1) ok_len += __shfl_xor(ok_len, d, 64);
-    if ((threadIdx.x & 63u) == 0 && ok_len) atomicAdd(reinterpret_cast<unsigned long long*>(result + 1), static_cast<unsigned long long>(ok_len));
+    ok_len = wave_sum(ok_len);
+    if ((threadIdx.x & 63u) == 0 && ok_len) atomic_add64(result + 1, ok_len);
 }
 
 // One workgroup per slot: [type:1][len:3 LE = payload + 4][masked crc:4 LE][payload]  (:233-261), k_frame_emit's chunk at its buffer's place.
@@ -126,19 +126,13 @@ __global__ __launch_bounds__(256) void k_fe_emit(const u32* __restrict__ c_owner
 }
 
 // ---- decode ----------------------------------------------------------------------------------------------------------------------------------
-// (the span tables FbSpans, the per-stream record FbStreams and walks A and B -- k_fd_candidates, k_fd_resolve -- are in frame_walk_device.h)
-// the chunk table over max_chunks slots (snp_frame_decode_device's rows, offsets absolute)
-struct FbRows {
-    u8* type;
-    u64 *body_off, *out_off;
-    u32 *body_len, *crc, *out_cap, *out_len, *owner;
-    i32* status;
-};
+// (the span table FbSpans, the chunk table ChunkRows and the per-span bodies are in frame_hop_device.h, the per-stream record FbStreams and walks A
+// and B -- k_fd_candidates, k_fd_resolve -- in frame_walk_device.h; a row's tag is its stream here)
 
-// C: the rows of every span of every decoded stream at their global slots (k_span_emit)
+// C: the rows of every span of every decoded stream at their global slots (k_span_emit), body and output offsets absolute
 __global__ __launch_bounds__(SNP_WAVE) void k_fd_emit(const u8* __restrict__ in, const u64* __restrict__ in_off, const u64* __restrict__ in_len,
                                                      const u64* __restrict__ out_off, u32 ns, const u64* __restrict__ sfirst, u32 max_spans,
-                                                     const u64* __restrict__ cfirst, u32 max_chunks, FbSpans t, FbStreams st, FbRows r)
+                                                     const u64* __restrict__ cfirst, u32 max_chunks, FbSpans t, FbStreams st, ChunkRows r)
 {
     const u32 g = blockIdx.x;
     if (lane_id() != 0 || g >= sfirst[ns]) return;
@@ -146,34 +140,16 @@ __global__ __launch_bounds__(SNP_WAVE) void k_fd_emit(const u8* __restrict__ in,
     if (sfirst[b + 1] > max_spans || cfirst[b + 1] > max_chunks) return;   // not walked, or not decoded
     const u64 e = t.entry[g];
     if (e == kNoEntry) return;
-    const u8* const p = in + in_off[b];
-    const u64 n = in_len[b];
-    const u32 nc_b = st.nc[b];
     const u64 row0 = cfirst[b], ib = in_off[b], ob = out_off[b];
-    u32 idx = t.chunk_base[g];
-    u64 off = t.out_base[g];
-    u64 ip = e;
-    const u64 s1 = (g - sfirst[b] + 1) * kSpan;
-    while (ip < s1 && idx < nc_b) {
-        const Hop h = frame_hop(p, n, ip);
-        if (h.kind == HOP_END || h.kind == HOP_ERR) break;
-        if (h.kind == HOP_DATA) {
-            const u64 row = row0 + idx;
-            r.type[row] = static_cast<u8>(h.type);
-            r.body_off[row] = ib + ip + 8;
-            r.body_len[row] = h.body_len;
-            r.crc[row] = h.crc;
-            r.out_off[row] = ob + off;
-            r.out_cap[row] = h.dec;
-            off += h.dec;
-            ++idx;
-        }
-        ip = h.next;
-    }
+    for_span_chunks(in + ib, in_len[b], e, (g - sfirst[b] + 1) * kSpan, t.chunk_base[g], st.nc[b], t.out_base[g],
+                    [&](const Hop& h, u64 ip, u32 idx, u64 off) {
+                        chunk_row_set(r, row0 + idx, h, ib + ip, ob + off);
+                        return true;
+                    });
 }
 
-// one thread per chunk slot: its decoded stream, or an empty raw chunk with the CRC of nothing (reads and writes nothing)
-__global__ __launch_bounds__(256) void k_fd_pad(u32 ns, const u64* __restrict__ cfirst, u32 max_chunks, FbRows r)
+// one thread per chunk slot: its decoded stream, or an empty row (the decoder reads and writes nothing for it)
+__global__ __launch_bounds__(256) void k_fd_pad(u32 ns, const u64* __restrict__ cfirst, u32 max_chunks, ChunkRows r)
 {
     const u32 c = blockIdx.x * 256u + threadIdx.x;
     if (c >= max_chunks) return;
@@ -182,22 +158,15 @@ __global__ __launch_bounds__(256) void k_fd_pad(u32 ns, const u64* __restrict__ 
         const u32 b = owner_of(cfirst, ns, c);
         if (cfirst[b + 1] <= max_chunks) owner = b;                     // (a stream with chunks was walked)
     }
-    r.owner[c] = owner;
-    if (owner == kNone) {
-        r.type[c] = 1;
-        r.body_off[c] = 0;
-        r.body_len[c] = 0;
-        r.crc[c] = kEmptyMaskedCrc;
-        r.out_off[c] = 0;
-        r.out_cap[c] = 0;
-    }
+    r.tag[c] = owner;
+    if (owner == kNone) chunk_row_clear(r, c, 0);
 }
 
-__global__ __launch_bounds__(256) void k_fd_fail(u32 max_chunks, FbRows r, FbStreams st)
+__global__ __launch_bounds__(256) void k_fd_fail(u32 max_chunks, ChunkRows r, FbStreams st)
 {
     const u32 c = blockIdx.x * 256u + threadIdx.x;
     if (c >= max_chunks) return;
-    const u32 b = r.owner[c];
+    const u32 b = r.tag[c];
     if (b != kNone && r.status[c] != SNP_OK) atomicMin(&st.fail[b], c);
 }
 
@@ -219,8 +188,8 @@ __global__ __launch_bounds__(256) void k_fd_verdict(u32 ns, const u64* __restric
         status[b] = s;
         out_len[b] = ok_len;
     }
-    for (u32 d = 32; d >= 1; d >>= 1) ok_len += __shfl_xor(ok_len, d, 64);
-    if ((threadIdx.x & 63u) == 0 && ok_len) atomicAdd(reinterpret_cast<unsigned long long*>(result + 1), static_cast<unsigned long long>(ok_len));
+    ok_len = wave_sum(ok_len);
+    if ((threadIdx.x & 63u) == 0 && ok_len) atomic_add64(result + 1, ok_len);
 }
 
 // ---- workspaces (every piece 256-byte aligned; nothing when there is no buffer) --------------------------------------------------------------
@@ -261,7 +230,7 @@ struct DecodeWork {
     u64 *sfirst, *cfirst, *part;
     FbStreams st;
     FbSpans sp;
-    FbRows r;
+    ChunkRows r;
     u64 bytes;
 };
 DecodeWork decode_work_layout(void* base, u32 nstreams, u32 max_chunks, u32 max_spans)
@@ -274,15 +243,7 @@ DecodeWork decode_work_layout(void* base, u32 nstreams, u32 max_chunks, u32 max_
     w.cfirst = k.take<u64>(ns + 1);
     w.part = k.take<u64>(scan_tiles_of(ns));
     carve_span_walk(k, ns, nsp, w.st, w.sp);
-    w.r.body_off = k.take<u64>(nc);
-    w.r.out_off = k.take<u64>(nc);
-    w.r.body_len = k.take<u32>(nc);
-    w.r.crc = k.take<u32>(nc);
-    w.r.out_cap = k.take<u32>(nc);
-    w.r.out_len = k.take<u32>(nc);
-    w.r.owner = k.take<u32>(nc);
-    w.r.status = k.take<i32>(nc);
-    w.r.type = k.take<u8>(nc);
+    w.r = carve_chunk_rows(k, nc);
     w.bytes = k.bytes();
     return w;
 }
@@ -361,10 +322,8 @@ snp_status snp_frame_decode_buffers_batch(snp_ctx* c, const uint8_t* in, const u
     if (ok && M) {
         if (S) hipLaunchKernelGGL(k_fd_emit, dim3(S), dim3(SNP_WAVE), 0, s, in, in_off, in_len, out_off, ns, w.sfirst, S, w.cfirst, M, w.sp, w.st, w.r);
         hipLaunchKernelGGL(k_fd_pad, dim3((M + 255u) / 256u), dim3(256), 0, s, ns, w.cfirst, M, w.r);
-        // decode + CRC verify of every slot (SnappyStreamDecompressor.cs:117-131), as snp_frame_decode_chunks_device
-        ok = c->check(hipGetLastError(), "frame buffers table") &&
-             c->launch_decompress(in, w.r.body_off, w.r.body_len, M, out, w.r.out_off, w.r.out_cap, w.r.out_len, w.r.status, w.r.type) &&
-             c->check(snp_launch_crc32c(out, w.r.out_off, w.r.out_len, M, 1 | c->crc_bits(), nullptr, w.r.crc, w.r.status, s), "frame buffers crc verify");
+        // decode + CRC verify of every slot, as snp_frame_decode_chunks_device
+        ok = c->check(hipGetLastError(), "frame buffers table") && c->decode_chunks(in, w.r, M, out);
         if (ok) hipLaunchKernelGGL(k_fd_fail, dim3((M + 255u) / 256u), dim3(256), 0, s, M, w.r, w.st);
     }
     if (ok) {

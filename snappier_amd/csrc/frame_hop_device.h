@@ -1,9 +1,14 @@
-// frame_hop_device.h -- one hop of a framed stream's chunk-header walk, and the span walk built on it: the device code that the one-stream
-// header walks (the serial one of framing.hip, k_frame_scan, and the span walk of frame_scan.hip: snp_frame_decode_device) and the batched
-// one (frame_buffers.hip, snp_frame_decode_buffers_batch) share.  The rules of one hop (frame_hop) are those of the host walk in
-// capi_frame.hip (scan_chunks); the block preamble and the expansion bound inside it are snp_rules.h's.
+// frame_hop_device.h -- what every header walk of a framed stream is made of, for ONE stream and one span of it: one hop of the chunk-header chain
+// (frame_hop, __host__ __device__: the host walk of capi_frame.hip is a loop over it too), the candidate test, the chain walk, the span table and
+// the chunk table with their places in a workspace, and the per-span bodies of the span walk -- the candidates of a span (walk A), the lookup of a
+// span's entry among the candidates of 64 spans (walk B), the hops over a span's data chunks from its entry (walk C) and the empty row.  Its users
+// are thin drivers that find their stream and span: the one-stream walks (framing.hip k_frame_scan, frame_scan.hip k_span_*:
+// snp_frame_decode_device), the many-stream walk (frame_walk_device.h k_fd_candidates, k_fd_resolve) and the kernels behind it (frame_buffers.hip,
+// frame_range.hip).  What belongs to MANY streams -- the per-stream record, the span slots of a batch, the launches -- is frame_walk_device.h.
+// The block preamble and the expansion bound inside a hop are snp_rules.h's.
 #pragma once
 #include "snp_rules.h"
+#include "work_carver.h"
 
 namespace {
 
@@ -12,6 +17,63 @@ constexpr u32 kWindow = 80 * 1024;          // > 8 + MaxCompressedLength(65536):
 constexpr u32 kMaxCand = 4;                 // candidates kept per span (the lowest plausible positions of its window)
 constexpr u32 kEmptyMaskedCrc = 0xa282ead8u;   // crc32c_mask(crc32c of no bytes)
 constexpr u64 kNoEntry = ~0ull;
+constexpr u32 kNone = 0xffffffffu;
+
+// ---- the two tables ------------------------------------------------------------------------------------------------------------------------------
+// per span slot, structure of arrays ([n][kMaxCand] for the candidates; count = candidates kept, the lowest positions); positions are stream-relative
+struct FbSpans {
+    u32* count;
+    u32* start_rel;     // start - span * kSpan
+    u64* exit;
+    u64* dec;
+    u32* ndata;
+    i32* stop;
+    // resolver -> emitter
+    u64* entry;         // true entry of the span, kNoEntry if the chain never starts a header inside it
+    u32* chunk_base;    // the stream's data chunks before the span
+    u64* out_base;      // the stream's decoded bytes before the span
+};
+inline FbSpans carve_spans(WorkCarver& k, u64 n)
+{
+    FbSpans sp;
+    sp.count = k.take<u32>(n);
+    sp.start_rel = k.take<u32>(n * kMaxCand);
+    sp.exit = k.take<u64>(n * kMaxCand);
+    sp.dec = k.take<u64>(n * kMaxCand);
+    sp.ndata = k.take<u32>(n * kMaxCand);
+    sp.stop = k.take<i32>(n * kMaxCand);
+    sp.entry = k.take<u64>(n);
+    sp.chunk_base = k.take<u32>(n);
+    sp.out_base = k.take<u64>(n);
+    return sp;
+}
+
+// the chunk table (ChunkRows, capi_internal.h) over n rows of a d_work workspace
+inline ChunkRows carve_chunk_rows(WorkCarver& k, u64 n)
+{
+    ChunkRows r;
+    r.body_off = k.take<u64>(n);
+    r.out_off = k.take<u64>(n);
+    r.body_len = k.take<u32>(n);
+    r.crc = k.take<u32>(n);
+    r.out_cap = k.take<u32>(n);
+    r.out_len = k.take<u32>(n);
+    r.tag = k.take<u32>(n);
+    r.status = k.take<i32>(n);
+    r.type = k.take<u8>(n);
+    return r;
+}
+// Row i as an empty raw chunk with the CRC of nothing: the decoder and the CRC verify read and write nothing for it and report OK, so they run
+// over a whole table without the host knowing how many rows are in use.  (A table with tags sets the row's tag itself.)
+__device__ __forceinline__ void chunk_row_clear(const ChunkRows& r, u64 i, u64 out_off)
+{
+    r.type[i] = 1;
+    r.body_off[i] = 0;
+    r.body_len[i] = 0;
+    r.crc[i] = kEmptyMaskedCrc;
+    r.out_off[i] = out_off;
+    r.out_cap[i] = 0;
+}
 
 enum HopKind : u32 { HOP_DATA = 0, HOP_SKIP = 1, HOP_END = 2, HOP_ERR = 3 };
 
@@ -23,8 +85,8 @@ struct Hop {
     u64 next;       // position of the next header
 };
 
-// One header at ip (< n or == n).  Same rules, in the same order, as scan_chunks (capi_frame.hip) / the reference reader.
-__device__ __forceinline__ Hop frame_hop(const u8* __restrict__ in, u64 n, u64 ip)
+// One header at ip (< n or == n): the rules of the reference reader, in its order.  The only statement of them: the host walk calls it too.
+__host__ __device__ __forceinline__ Hop frame_hop(const u8* __restrict__ in, u64 n, u64 ip)
 {
     Hop h{};
     h.next = ip;
@@ -48,7 +110,7 @@ __device__ __forceinline__ Hop frame_hop(const u8* __restrict__ in, u64 n, u64 i
             const snp_preamble pre = snp_read_preamble(b[2] | (static_cast<u64>(b[3]) << 32), size - 4);
             if (pre.end != SNP_PRE_DONE || pre.value > 0x7fffffffu) { h.kind = HOP_ERR; h.err = SNP_ERR_BAD_LENGTH; return h; }
             dec = pre.value;
-            // (such a chunk can only end "Incomplete Snappy block.": capi_frame.hip scan_chunks)
+            // a chunk that declares more than its body can possibly produce (snp_rules.h) can only end "Incomplete Snappy block."
             if (dec > snp_max_expansion(size - 4 - pre.bytes)) { h.kind = HOP_ERR; h.err = SNP_ERR_INCOMPLETE; return h; }
         }
         h.kind = HOP_DATA;
@@ -61,6 +123,17 @@ __device__ __forceinline__ Hop frame_hop(const u8* __restrict__ in, u64 n, u64 i
     if (t < 0x80) { h.kind = HOP_ERR; h.err = SNP_ERR_CHUNK_TYPE; return h; }   // :182-185
     h.kind = HOP_SKIP;                                                  // 0x80..0xff skipped unvalidated  :187-196
     return h;
+}
+
+// Row i of a chunk table as the data chunk a hop found: its header at byte `header` of the input, its output at out_off.
+__device__ __forceinline__ void chunk_row_set(const ChunkRows& r, u64 i, const Hop& h, u64 header, u64 out_off)
+{
+    r.type[i] = static_cast<u8>(h.type);
+    r.body_off[i] = header + SNP_CHUNK_HEADER_LEN;
+    r.body_len[i] = h.body_len;
+    r.crc[i] = h.crc;
+    r.out_off[i] = out_off;
+    r.out_cap[i] = h.dec;
 }
 
 // "Could the true chain enter here?"  Only shapes a spec-conforming writer emits are candidates (a data chunk of at most
@@ -110,6 +183,125 @@ __device__ __forceinline__ Chain follow_chain(const u8* __restrict__ in, u64 n, 
     if (c.stop == 0 && ip >= n) c.stop = ip == n ? -1 : 0;   // ip > n cannot happen (a body never runs past n)
     c.exit = ip;
     return c;
+}
+
+// ---- the per-span bodies of the span walk ----------------------------------------------------------------------------------------------------------
+// Walk A, one wavefront per span: the candidates of span k of the stream (p, n) into s_cand, their count into *s_n (both in LDS) and back.  Span 0
+// enters at byte 0, whatever is there.  Otherwise the kMaxCand LOWEST plausible positions of the span's first kWindow bytes: the true entry is the
+// first true header of the span, and fewer than kMaxCand false positives precede it except in adversarial payloads (then the resolver walks the
+// span itself).  All lanes must call it.
+__device__ __forceinline__ u32 span_candidates(const u8* __restrict__ p, u64 n, u64 k, u32* s_cand, u32* s_n)
+{
+    const u32 lane = lane_id();
+    const u64 s0 = k * kSpan;
+    const u64 s1 = s0 + kSpan < n ? s0 + kSpan : n;
+    if (lane == 0) *s_n = 0;
+    __syncthreads();
+    if (k == 0) {
+        if (lane == 0) { s_cand[0] = 0; *s_n = 1; }
+    } else {
+        const u64 wend = s0 + kWindow < s1 ? s0 + kWindow : s1;
+        for (u64 base = s0; base < wend; base += SNP_WAVE) {
+            const u64 q = base + lane;
+            const bool ok = q < wend && plausible_start(p, n, q);
+            const u64 m = ballot64(ok);
+            if (m) {
+                const u32 have = *s_n;
+                if (ok) {
+                    const u32 idx = have + static_cast<u32>(__builtin_popcountll(m & lanes_below(lane)));
+                    if (idx < kMaxCand) s_cand[idx] = static_cast<u32>(q - s0);
+                }
+                __syncthreads();
+                if (lane == 0) { const u32 tot = have + static_cast<u32>(__builtin_popcountll(m)); *s_n = tot < kMaxCand ? tot : kMaxCand; }
+                __syncthreads();
+                if (*s_n == kMaxCand) break;
+            }
+        }
+    }
+    __syncthreads();
+    return *s_n;
+}
+// ... and slot g of the span table: lane c follows candidate c's chain to the end of the span
+__device__ __forceinline__ void span_candidates_row(const FbSpans& t, u64 g, const u8* __restrict__ p, u64 n, u64 k, const u32* s_cand, u32 count)
+{
+    const u32 lane = lane_id();
+    if (lane == 0) t.count[g] = count;
+    if (lane < count) {
+        const Chain c = follow_chain(p, n, k * kSpan + s_cand[lane], (k + 1) * kSpan);
+        const u64 i = g * kMaxCand + lane;
+        t.start_rel[i] = s_cand[lane];
+        t.exit[i] = c.exit;
+        t.dec[i] = c.dec;
+        t.ndata[i] = c.ndata;
+        t.stop[i] = c.stop;
+    }
+}
+
+// Walk B, one wavefront per stream: lane l holds the candidates of span batch0 + l of the stream whose first span slot is g0; the chain is
+// followed with readlane, so a hop from span to span costs ~20 scalar instructions and no memory.
+struct SpanBatch {
+    u64 batch0 = ~0ull;                                                 // first span of the batch held in registers
+    u32 srel[kMaxCand] = {}, cnd[kMaxCand] = {};
+    i32 cst[kMaxCand] = {};
+    u64 cex[kMaxCand] = {}, cde[kMaxCand] = {};
+
+    // makes span k one of the 64 held (k is wave-uniform)
+    __device__ __forceinline__ void load(const FbSpans& t, u64 g0, u64 nspans, u64 k)
+    {
+        if (k >= batch0 && k < batch0 + SNP_WAVE) return;
+        batch0 = k;
+        const u64 mine = batch0 + lane_id();
+        const u64 gi = g0 + mine;
+        const u32 cnt = mine < nspans ? t.count[gi] : 0;
+#pragma unroll
+        for (u32 j = 0; j < kMaxCand; ++j) {
+            const bool have = mine < nspans && j < cnt;
+            srel[j] = have ? t.start_rel[gi * kMaxCand + j] : 0xffffffffu;
+            cex[j] = have ? t.exit[gi * kMaxCand + j] : 0;
+            cde[j] = have ? t.dec[gi * kMaxCand + j] : 0;
+            cnd[j] = have ? t.ndata[gi * kMaxCand + j] : 0;
+            cst[j] = have ? t.stop[gi * kMaxCand + j] : 0;
+        }
+    }
+    // the chain of the candidate of span k (held) that starts at e, if there is one
+    __device__ __forceinline__ bool find(u64 e, u64 k, Chain* c) const
+    {
+        const u32 l = static_cast<u32>(k - batch0);
+        const u32 rel = static_cast<u32>(e - k * kSpan);
+        bool found = false;
+#pragma unroll
+        for (u32 j = 0; j < kMaxCand; ++j) {
+            if (!found && read_lane(srel[j], l) == rel) {
+                found = true;
+                c->exit = (static_cast<u64>(read_lane(static_cast<u32>(cex[j] >> 32), l)) << 32) | read_lane(static_cast<u32>(cex[j]), l);
+                c->dec = (static_cast<u64>(read_lane(static_cast<u32>(cde[j] >> 32), l)) << 32) | read_lane(static_cast<u32>(cde[j]), l);
+                c->ndata = read_lane(cnd[j], l);
+                c->stop = static_cast<i32>(read_lane(static_cast<u32>(cst[j]), l));
+            }
+        }
+        return found;
+    }
+};
+
+// Walk C, one lane: the hops from `entry` while the header lies below span_end and the data chunk index below idx_end.  visit(h, ip, idx, off) sees
+// every data chunk -- the hop, its header's position, its index in the stream and the decoded bytes before it -- and returns false to stop.
+// Returns what ended the hops, as Chain::stop: 0 a bound or the visitor, -1 the clean end of the stream, > 0 the status of a bad header.
+template <class Visit>
+__device__ __forceinline__ i32 for_span_chunks(const u8* __restrict__ p, u64 n, u64 entry, u64 span_end, u32 idx, u32 idx_end, u64 off, Visit visit)
+{
+    u64 ip = entry;
+    while (ip < span_end && idx < idx_end) {
+        const Hop h = frame_hop(p, n, ip);
+        if (h.kind == HOP_END) return -1;
+        if (h.kind == HOP_ERR) return h.err;
+        if (h.kind == HOP_DATA) {
+            if (!visit(h, ip, idx, off)) break;
+            off += h.dec;
+            ++idx;
+        }
+        ip = h.next;
+    }
+    return 0;
 }
 
 }  // namespace

@@ -9,7 +9,7 @@
 //   window    one thread per stream: lo, hi, "the window does not fit out_cap" (such a stream selects nothing); its two edge slots, two rows of
 //             the edge table and its failure word emptied
 //   select    one wavefront per span slot: ONLY a span whose decoded bytes [out_base, the next entered span's out_base) meet the window is hopped
-//             (k_fd_emit's loop); it counts the span's interior chunks and records an edge chunk in its stream's head or tail slot
+//             (for_span_chunks, frame_hop_device.h); it counts the span's interior chunks and records an edge chunk in its stream's head or tail slot
 //   scans     interior counts over the span slots -> each span's (and so each stream's) first row (d_result[0]); over the edge slots, the decoded
 //             sizes -> each edge's place in the scratch arena (d_result[4]), and the slots in use -> each edge's row in the edge table
 //   admit     one thread per stream: spans, interior rows and edge bytes within their bounds -> its edges' rows.  The edge table is COMPACT
@@ -17,8 +17,8 @@
 //             17.5 ms for the 163 840 edges of the 64 KiB shape, against 9.3 ms for the same chunks as a dense table
 //   emit      every row an empty raw chunk with the CRC of nothing (k_fd_pad), then one wavefront per span slot with interior chunks: their rows,
 //             the output at out_off[b] + (s - lo)
-//   decode    snp_ctx::launch_decompress and the verifying snp_launch_crc32c over the interior table into `out`, and the same pair over the 2 x
-//             nstreams rows of the edge table into scratch (two calls: launch_decompress takes one output base)
+//   decode    snp_ctx::decode_chunks (decode + CRC verify) over the interior table into `out`, and over the 2 x nstreams rows of the edge table
+//             into scratch (two calls: the decoder takes one output base)
 //   trim      one workgroup per edge row: the part of an OK edge inside the window, scratch -> out
 //   verdict   one thread per failing row: atomicMin of (its place in the stream, status) into the stream's word (k_fd_fail); one thread per
 //             stream: the head edge, else the first failing interior row, else the tail edge, else the walk's tail, else the capacity, else OK
@@ -39,42 +39,18 @@ struct FrStreams {
     u32* flags;
     u64* fail;          // min over the failing interior rows of (1 + place among the stream's rows) << 8 | status
 };
-// the interior chunk table over max_chunks slots (FbRows of frame_buffers.hip)
-struct FrRows {
-    u8* type;
-    u64 *body_off, *out_off;
-    u32 *body_len, *crc, *out_cap, *out_len, *owner;
-    i32* status;
-};
 // two edge slots per stream, where k_fr_select records what it finds (head: 2 b, tail: 2 b + 1); dec == 0: an empty slot
 struct FrEdges {
     u8* type;
     u64 *body_off, *start, *place, *rank;   // start: s, the chunk's first decoded byte in its stream; place, rank: the scans of dec and of dec != 0 (2 ns + 1 each)
     u32 *body_len, *crc, *dec;
 };
-// the edge table the decoder sees, 2 ns rows: the edges of the admitted streams in stream order, then empty rows
-struct FrEdgeRows {
-    u8* type;
-    u64 *body_off, *out_off;
-    u32 *body_len, *crc, *out_cap, *out_len, *src;   // src: the edge slot the row came from, kNone for an empty row
-    i32* status;
-};
-
-// an empty raw chunk with the CRC of nothing (k_fd_pad)
-__device__ __forceinline__ void edge_row_clear(const FrEdgeRows& c, u64 row)
-{
-    c.src[row] = kNone;
-    c.type[row] = 1;
-    c.body_off[row] = 0;
-    c.body_len[row] = 0;
-    c.crc[row] = kEmptyMaskedCrc;
-    c.out_off[row] = 0;
-    c.out_cap[row] = 0;
-}
+// The two chunk tables (ChunkRows): the interior rows over max_chunks slots, tagged with their stream; and the edge table the decoder sees, 2 ns
+// rows -- the edges of the admitted streams in stream order, then empty rows -- tagged with the edge slot the row came from.
 
 __global__ __launch_bounds__(256) void k_fr_window(u32 ns, const u64* __restrict__ sfirst, u32 max_spans, const u64* __restrict__ range_off,
                                                   const u64* __restrict__ range_len, const u64* __restrict__ out_cap, FbStreams st, FrStreams w,
-                                                  FrEdges e, FrEdgeRows c, u64* __restrict__ result)
+                                                  FrEdges e, ChunkRows c, u64* __restrict__ result)
 {
     const u32 b = blockIdx.x * 256u + threadIdx.x;
     if (b == 0) { result[4] = 0; result[5] = 0; }
@@ -89,8 +65,10 @@ __global__ __launch_bounds__(256) void k_fr_window(u32 ns, const u64* __restrict
     w.fail[b] = kNoFail;
     e.dec[2ull * b] = 0;
     e.dec[2ull * b + 1] = 0;
-    edge_row_clear(c, 2ull * b);
-    edge_row_clear(c, 2ull * b + 1);
+    for (u64 row = 2ull * b; row < 2ull * b + 2; ++row) {
+        c.tag[row] = kNone;
+        chunk_row_clear(c, row, 0);
+    }
 }
 
 // Where span g's decoded bytes end: the out_base of the stream's next span that the chain entered, else the stream's total.  (A span the chain
@@ -115,37 +93,27 @@ __global__ __launch_bounds__(SNP_WAVE) void k_fr_select(const u8* __restrict__ i
         const u64 entry = sfirst[b + 1] <= max_spans && !(w.flags[b] & kSmall) ? t.entry[g] : kNoEntry;
         if (entry != kNoEntry) {
             const u64 lo = w.lo[b], hi = w.hi[b];
-            u64 off = t.out_base[g];
+            const u64 off0 = t.out_base[g];
             // the test that makes a narrow window in a long stream cheap: a span wholly outside the window is not hopped
-            if (off < hi && span_out_end(t, g, sfirst[b + 1], st.total[b]) > lo) {
-                const u8* const p = in + in_off[b];
-                const u64 n = in_len[b], ib = in_off[b];
-                const u32 nc_b = st.nc[b];
-                u32 idx = t.chunk_base[g];
-                u64 ip = entry;
-                const u64 s1 = (g - sfirst[b] + 1) * kSpan;
-                while (ip < s1 && idx < nc_b && off < hi) {
-                    const Hop h = frame_hop(p, n, ip);
-                    if (h.kind == HOP_END || h.kind == HOP_ERR) break;
-                    if (h.kind == HOP_DATA) {
-                        if (h.dec > 0 && off + h.dec > lo) {            // selected (off < hi)
-                            if (off >= lo && off + h.dec <= hi) {
-                                ++cnt;
-                            } else {                                    // an edge: the one chunk that holds lo is the head, any other the tail
-                                const u64 slot = 2ull * b + (off > lo ? 1 : 0);
-                                e.type[slot] = static_cast<u8>(h.type);
-                                e.body_off[slot] = ib + ip + 8;
-                                e.body_len[slot] = h.body_len;
-                                e.crc[slot] = h.crc;
-                                e.dec[slot] = h.dec;
-                                e.start[slot] = off;
-                            }
-                        }
-                        off += h.dec;
-                        ++idx;
-                    }
-                    ip = h.next;
-                }
+            if (off0 < hi && span_out_end(t, g, sfirst[b + 1], st.total[b]) > lo) {
+                const u64 ib = in_off[b];
+                for_span_chunks(in + ib, in_len[b], entry, (g - sfirst[b] + 1) * kSpan, t.chunk_base[g], st.nc[b], off0,
+                                [&](const Hop& h, u64 ip, u32, u64 off) {
+                                    if (h.dec > 0 && off + h.dec > lo) {            // selected (off < hi)
+                                        if (off >= lo && off + h.dec <= hi) {
+                                            ++cnt;
+                                        } else {                        // an edge: the one chunk that holds lo is the head, any other the tail
+                                            const u64 slot = 2ull * b + (off > lo ? 1 : 0);
+                                            e.type[slot] = static_cast<u8>(h.type);
+                                            e.body_off[slot] = ib + ip + SNP_CHUNK_HEADER_LEN;
+                                            e.body_len[slot] = h.body_len;
+                                            e.crc[slot] = h.crc;
+                                            e.dec[slot] = h.dec;
+                                            e.start[slot] = off;
+                                        }
+                                    }
+                                    return off + h.dec < hi;            // the chunks behind the window are not hopped
+                                });
             }
         }
     }
@@ -164,7 +132,7 @@ struct ScanEdgeCount {
 // Admission (in stream order: the three sums only grow), the rows of the admitted streams' edges with their places in the scratch arena,
 // d_result[4] and [5].  (A rank is below 2 ns and belongs to one edge: every row is written by one thread, after k_fr_window emptied it.)
 __global__ __launch_bounds__(256) void k_fr_admit(u32 ns, const u64* __restrict__ sfirst, u32 max_spans, const u64* __restrict__ ispan, u32 max_chunks,
-                                                 u64 edge_cap, FrStreams w, FrEdges e, FrEdgeRows c, u64* __restrict__ result)
+                                                 u64 edge_cap, FrStreams w, FrEdges e, ChunkRows c, u64* __restrict__ result)
 {
     const u32 b = blockIdx.x * 256u + threadIdx.x;
     u64 nsel = 0;
@@ -176,7 +144,7 @@ __global__ __launch_bounds__(256) void k_fr_admit(u32 ns, const u64* __restrict_
             ++nsel;
             if (!ok) continue;
             const u64 row = e.rank[slot];
-            c.src[row] = static_cast<u32>(slot);
+            c.tag[row] = static_cast<u32>(slot);
             c.type[row] = e.type[slot];
             c.body_off[row] = e.body_off[slot];
             c.body_len[row] = e.body_len[slot];
@@ -189,29 +157,24 @@ __global__ __launch_bounds__(256) void k_fr_admit(u32 ns, const u64* __restrict_
             nsel += ispan[max_spans];
         }
     }
-    for (u32 d = 32; d >= 1; d >>= 1) nsel += __shfl_xor(nsel, d, 64);
-    if ((threadIdx.x & 63u) == 0 && nsel) atomicAdd(reinterpret_cast<unsigned long long*>(result + 5), static_cast<unsigned long long>(nsel));
+    nsel = wave_sum(nsel);
+    if ((threadIdx.x & 63u) == 0 && nsel) atomic_add64(result + 5, nsel);
 }
 
-// every interior slot an empty raw chunk with the CRC of nothing, owned by no stream (k_fd_pad); k_fr_emit then fills the rows in use
-__global__ __launch_bounds__(256) void k_fr_pad(u32 max_chunks, FrRows r)
+// every interior slot an empty row owned by no stream (k_fd_pad); k_fr_emit then fills the rows in use
+__global__ __launch_bounds__(256) void k_fr_pad(u32 max_chunks, ChunkRows r)
 {
     const u32 c = blockIdx.x * 256u + threadIdx.x;
     if (c >= max_chunks) return;
-    r.owner[c] = kNone;
-    r.type[c] = 1;
-    r.body_off[c] = 0;
-    r.body_len[c] = 0;
-    r.crc[c] = kEmptyMaskedCrc;
-    r.out_off[c] = 0;
-    r.out_cap[c] = 0;
+    r.tag[c] = kNone;
+    chunk_row_clear(r, c, 0);
 }
 
 // the interior rows of every span of every admitted stream: the hops of k_fr_select again, only where it counted a row
 __global__ __launch_bounds__(SNP_WAVE) void k_fr_emit(const u8* __restrict__ in, const u64* __restrict__ in_off, const u64* __restrict__ in_len,
                                                      const u64* __restrict__ out_off, u32 ns, const u64* __restrict__ sfirst, u32 max_spans,
                                                      const u64* __restrict__ ispan, const u32* __restrict__ icount, u32 max_chunks, FbSpans t,
-                                                     FbStreams st, FrStreams w, FrRows r)
+                                                     FbStreams st, FrStreams w, ChunkRows r)
 {
     const u32 g = blockIdx.x;
     if (lane_id() != 0 || g >= sfirst[ns]) return;
@@ -219,44 +182,28 @@ __global__ __launch_bounds__(SNP_WAVE) void k_fr_emit(const u8* __restrict__ in,
     if (cnt == 0) return;                                               // (a span with rows: its stream was walked and entered the span)
     const u32 b = owner_of(sfirst, ns, g);
     if (!(w.flags[b] & kAdmitted)) return;
-    const u8* const p = in + in_off[b];
-    const u64 n = in_len[b], ib = in_off[b], ob = out_off[b], lo = w.lo[b], hi = w.hi[b];
-    const u32 nc_b = st.nc[b];
+    const u64 ib = in_off[b], ob = out_off[b], lo = w.lo[b], hi = w.hi[b];
     u64 row = ispan[g];
     const u64 row_end = row + cnt;                                      // <= ispan[sfirst[b + 1]] <= max_chunks: the stream is admitted
     if (row_end > max_chunks) return;
-    u32 idx = t.chunk_base[g];
-    u64 off = t.out_base[g];
-    u64 ip = t.entry[g];
-    const u64 s1 = (g - sfirst[b] + 1) * kSpan;
-    while (ip < s1 && idx < nc_b && off < hi && row < row_end) {
-        const Hop h = frame_hop(p, n, ip);
-        if (h.kind == HOP_END || h.kind == HOP_ERR) break;
-        if (h.kind == HOP_DATA) {
-            if (h.dec > 0 && off >= lo && off + h.dec <= hi) {
-                r.owner[row] = b;
-                r.type[row] = static_cast<u8>(h.type);
-                r.body_off[row] = ib + ip + 8;
-                r.body_len[row] = h.body_len;
-                r.crc[row] = h.crc;
-                r.out_off[row] = ob + (off - lo);
-                r.out_cap[row] = h.dec;
-                ++row;
-            }
-            off += h.dec;
-            ++idx;
-        }
-        ip = h.next;
-    }
+    for_span_chunks(in + ib, in_len[b], t.entry[g], (g - sfirst[b] + 1) * kSpan, t.chunk_base[g], st.nc[b], t.out_base[g],
+                    [&](const Hop& h, u64 ip, u32, u64 off) {
+                        if (h.dec > 0 && off >= lo && off + h.dec <= hi) {
+                            r.tag[row] = b;
+                            chunk_row_set(r, row, h, ib + ip, ob + (off - lo));
+                            ++row;
+                        }
+                        return off + h.dec < hi && row < row_end;
+                    });
 }
 
 // One workgroup per edge row: an OK edge's bytes inside the window, scratch -> out.  (A row in use belongs to an admitted stream whose window
 // fits its out_cap: max(s, lo) - lo + the bytes copied = min(s + d, hi) - lo <= hi - lo <= out_cap.)
-__global__ __launch_bounds__(256) void k_fr_trim(FrEdgeRows c, FrEdges e, FrStreams w, const u8* __restrict__ scratch, u8* __restrict__ out,
+__global__ __launch_bounds__(256) void k_fr_trim(ChunkRows c, FrEdges e, FrStreams w, const u8* __restrict__ scratch, u8* __restrict__ out,
                                                 const u64* __restrict__ out_off)
 {
     const u64 row = blockIdx.x;
-    const u32 slot = c.src[row];
+    const u32 slot = c.tag[row];
     if (slot == kNone) return;
     const u32 d = c.out_cap[row];
     if (c.status[row] != SNP_OK || c.out_len[row] != d) return;
@@ -268,11 +215,11 @@ __global__ __launch_bounds__(256) void k_fr_trim(FrEdgeRows c, FrEdges e, FrStre
 }
 
 // k_fd_fail over the interior table, keyed by the row's place in its stream
-__global__ __launch_bounds__(256) void k_fr_fail(u32 max_chunks, FrRows r, const u64* __restrict__ sfirst, const u64* __restrict__ ispan, FrStreams w)
+__global__ __launch_bounds__(256) void k_fr_fail(u32 max_chunks, ChunkRows r, const u64* __restrict__ sfirst, const u64* __restrict__ ispan, FrStreams w)
 {
     const u32 c = blockIdx.x * 256u + threadIdx.x;
     if (c >= max_chunks) return;
-    const u32 b = r.owner[c];
+    const u32 b = r.tag[c];
     if (b == kNone || r.status[c] == SNP_OK) return;
     const u64 key = ((1 + (c - ispan[sfirst[b]])) << 8) | static_cast<u64>(r.status[c] & 0xff);
     atomicMin(reinterpret_cast<unsigned long long*>(w.fail + b), static_cast<unsigned long long>(key));
@@ -280,7 +227,7 @@ __global__ __launch_bounds__(256) void k_fr_fail(u32 max_chunks, FrRows r, const
 
 // the stream's verdict: the first failing selected chunk in stream order (head edge, interior rows, tail edge), else the error that ended the
 // walk, else the capacity, else OK with hi - lo bytes.  result[1] += the OK lengths (one atomic per wavefront).
-__global__ __launch_bounds__(256) void k_fr_verdict(u32 ns, FbStreams st, FrStreams w, FrEdges e, FrEdgeRows c, u64* __restrict__ out_len,
+__global__ __launch_bounds__(256) void k_fr_verdict(u32 ns, FbStreams st, FrStreams w, FrEdges e, ChunkRows c, u64* __restrict__ out_len,
                                                    i32* __restrict__ status, u64* __restrict__ result)
 {
     const u32 b = blockIdx.x * 256u + threadIdx.x;
@@ -300,8 +247,8 @@ __global__ __launch_bounds__(256) void k_fr_verdict(u32 ns, FbStreams st, FrStre
         status[b] = s;
         out_len[b] = ok_len;
     }
-    for (u32 d = 32; d >= 1; d >>= 1) ok_len += __shfl_xor(ok_len, d, 64);
-    if ((threadIdx.x & 63u) == 0 && ok_len) atomicAdd(reinterpret_cast<unsigned long long*>(result + 1), static_cast<unsigned long long>(ok_len));
+    ok_len = wave_sum(ok_len);
+    if ((threadIdx.x & 63u) == 0 && ok_len) atomic_add64(result + 1, ok_len);
 }
 
 // ---- workspace (every piece 256-byte aligned; nothing when there is no stream) -----------------------------------------------------------------
@@ -314,9 +261,9 @@ struct RangeWork {
     FbStreams st;
     FbSpans sp;
     FrStreams w;
-    FrRows r;
+    ChunkRows r;         // interior rows
     FrEdges e;
-    FrEdgeRows c;
+    ChunkRows c;         // edge rows
     u8* scratch;
     u64 bytes;
 };
@@ -335,15 +282,7 @@ RangeWork range_work_layout(void* base, u32 nstreams, u32 max_chunks, u32 max_sp
     k.w.flags = c.take<u32>(ns);
     k.icount = c.take<u32>(nsp);
     k.ispan = c.take<u64>(nsp + 1);
-    k.r.body_off = c.take<u64>(nc);
-    k.r.out_off = c.take<u64>(nc);
-    k.r.body_len = c.take<u32>(nc);
-    k.r.crc = c.take<u32>(nc);
-    k.r.out_cap = c.take<u32>(nc);
-    k.r.out_len = c.take<u32>(nc);
-    k.r.owner = c.take<u32>(nc);
-    k.r.status = c.take<i32>(nc);
-    k.r.type = c.take<u8>(nc);
+    k.r = carve_chunk_rows(c, nc);
     k.e.body_off = c.take<u64>(ne);
     k.e.start = c.take<u64>(ne);
     k.e.place = c.take<u64>(ne + 1);
@@ -352,15 +291,7 @@ RangeWork range_work_layout(void* base, u32 nstreams, u32 max_chunks, u32 max_sp
     k.e.crc = c.take<u32>(ne);
     k.e.dec = c.take<u32>(ne);
     k.e.type = c.take<u8>(ne);
-    k.c.body_off = c.take<u64>(ne);
-    k.c.out_off = c.take<u64>(ne);
-    k.c.body_len = c.take<u32>(ne);
-    k.c.crc = c.take<u32>(ne);
-    k.c.out_cap = c.take<u32>(ne);
-    k.c.out_len = c.take<u32>(ne);
-    k.c.src = c.take<u32>(ne);
-    k.c.status = c.take<i32>(ne);
-    k.c.type = c.take<u8>(ne);
+    k.c = carve_chunk_rows(c, ne);
     k.scratch = c.take<u8>(edge_cap);
     k.bytes = c.bytes();
     return k;
@@ -411,15 +342,12 @@ snp_status snp_frame_decode_range_batch(snp_ctx* c, const uint8_t* in, const uin
         hipLaunchKernelGGL(k_fr_pad, dim3((M + 255u) / 256u), dim3(256), 0, s, M, w.r);
         if (S) hipLaunchKernelGGL(k_fr_emit, dim3(S), dim3(SNP_WAVE), 0, s, in, in_off, in_len, out_off, ns, w.sfirst, S, w.ispan, w.icount, M, w.sp,
                                   w.st, w.w, w.r);
-        // decode + CRC verify of every interior slot, straight into out (SnappyStreamDecompressor.cs:117-131)
-        ok = c->check(hipGetLastError(), "frame range table") &&
-             c->launch_decompress(in, w.r.body_off, w.r.body_len, M, out, w.r.out_off, w.r.out_cap, w.r.out_len, w.r.status, w.r.type) &&
-             c->check(snp_launch_crc32c(out, w.r.out_off, w.r.out_len, M, 1 | c->crc_bits(), nullptr, w.r.crc, w.r.status, s), "frame range crc verify");
+        // decode + CRC verify of every interior slot, straight into out
+        ok = c->check(hipGetLastError(), "frame range table") && c->decode_chunks(in, w.r, M, out);
         if (ok) hipLaunchKernelGGL(k_fr_fail, dim3((M + 255u) / 256u), dim3(256), 0, s, M, w.r, w.sfirst, w.ispan, w.w);
     }
     // the edges, whole, into scratch; then their parts inside the windows
-    ok = ok && c->launch_decompress(in, w.c.body_off, w.c.body_len, E, w.scratch, w.c.out_off, w.c.out_cap, w.c.out_len, w.c.status, w.c.type) &&
-         c->check(snp_launch_crc32c(w.scratch, w.c.out_off, w.c.out_len, E, 1 | c->crc_bits(), nullptr, w.c.crc, w.c.status, s), "frame range edge crc verify");
+    ok = ok && c->decode_chunks(in, w.c, E, w.scratch);
     if (ok) {
         hipLaunchKernelGGL(k_fr_trim, dim3(E), dim3(256), 0, s, w.c, w.e, w.w, w.scratch, out, out_off);
         hipLaunchKernelGGL(k_fr_verdict, dim3(groups), dim3(256), 0, s, ns, w.st, w.w, w.e, w.c, out_len, status, d_result);

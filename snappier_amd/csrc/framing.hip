@@ -112,10 +112,7 @@ __global__ __launch_bounds__(256) void k_frame_emit(const u8* __restrict__ raw, 
 // preamble).  One lane walks; the table it writes is exactly what the host walk in capi_frame.hip produces.  Entries past the last data
 // chunk are filled as empty uncompressed chunks so that the decode and CRC launches can run over max_chunks without
 // knowing the count on the host.
-__global__ __launch_bounds__(SNP_WAVE) void k_frame_scan(const u8* __restrict__ in, u64 n, u64 cap, u32 max_chunks,
-                                                        u8* __restrict__ type, u64* __restrict__ body_off,
-                                                        u32* __restrict__ body_len, u32* __restrict__ crc,
-                                                        u64* __restrict__ out_off, u32* __restrict__ out_cap,
+__global__ __launch_bounds__(SNP_WAVE) void k_frame_scan(const u8* __restrict__ in, u64 n, u64 cap, u32 max_chunks, ChunkRows r,
                                                         u64* __restrict__ hdr /* total, tail status, chunks */)
 {
     __shared__ u64 s_total;
@@ -124,18 +121,14 @@ __global__ __launch_bounds__(SNP_WAVE) void k_frame_scan(const u8* __restrict__ 
         u64 ip = 0, total = 0;
         u32 nc = 0;
         i32 tail = SNP_OK;
+        // for_span_chunks (frame_hop_device.h) over the whole stream, written out: as its visitor this loop came out 35 instructions longer
         for (;;) {
             const Hop h = frame_hop(in, n, ip);
             if (h.kind == HOP_END) break;
             if (h.kind == HOP_ERR) { tail = h.err; break; }
             if (h.kind == HOP_DATA) {
                 if (nc == max_chunks) { tail = SNP_ERR_OUTPUT_TOO_SMALL; break; }   // chunk table full
-                type[nc] = static_cast<u8>(h.type);
-                body_off[nc] = ip + 8;
-                body_len[nc] = h.body_len;
-                crc[nc] = h.crc;
-                out_off[nc] = total;
-                out_cap[nc] = h.dec;
+                chunk_row_set(r, nc, h, ip, total);
                 total += h.dec;
                 ++nc;
             }
@@ -150,14 +143,7 @@ __global__ __launch_bounds__(SNP_WAVE) void k_frame_scan(const u8* __restrict__ 
     }
     __syncthreads();
     const u64 total = s_total;
-    for (u32 k = s_nc + threadIdx.x; k < max_chunks; k += SNP_WAVE) {
-        type[k] = 1;
-        body_off[k] = 0;
-        body_len[k] = 0;
-        crc[k] = kEmptyMaskedCrc;
-        out_off[k] = total;
-        out_cap[k] = 0;
-    }
+    for (u32 k = s_nc + threadIdx.x; k < max_chunks; k += SNP_WAVE) chunk_row_clear(r, k, total);
 }
 
 // The stream's verdict: the first failing chunk in stream order (as the sequential reference would throw), else the
@@ -225,12 +211,9 @@ extern "C" hipError_t snp_launch_frame_emit(const u8* raw, const u64* in_off, co
     return hipGetLastError();
 }
 
-extern "C" hipError_t snp_launch_frame_scan(const u8* in, u64 n, u64 cap, u32 max_chunks, u8* type, u64* body_off,
-                                            u32* body_len, u32* crc, u64* out_off, u32* out_cap, u64* hdr,
-                                            hipStream_t stream)
+extern "C" hipError_t snp_launch_frame_scan(const u8* in, u64 n, u64 cap, u32 max_chunks, const ChunkRows& r, u64* hdr, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_frame_scan, dim3(1), dim3(SNP_WAVE), 0, stream, in, n, cap, max_chunks, type, body_off, body_len,
-                       crc, out_off, out_cap, hdr);
+    hipLaunchKernelGGL(k_frame_scan, dim3(1), dim3(SNP_WAVE), 0, stream, in, n, cap, max_chunks, r, hdr);
     return hipGetLastError();
 }
 

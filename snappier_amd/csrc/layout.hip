@@ -4,7 +4,7 @@
 // Built into libsnappier_hip_layout.so (C-ABI: include/snappier_hip_layout.h), linked against libsnappier_hip.so.  DESIGN.md 4.12.
 //
 // Blocks:
-//   probe     one thread per buffer: the varint preamble (at most 5 bytes) -> status, declared; the expansion rule of scan_chunks
+//   probe     one thread per buffer: the varint preamble (at most 5 bytes) -> status, declared; the expansion rule of frame_hop
 //   scan      slot = declared rounded up to align for an OK buffer, else 0 -> each buffer's offset (scan_tiles.h, multi-workgroup)
 //   first     one thread per buffer: the OK buffers whose range ends beyond arena_cap, minimum index into d_result[1] (one atomic per wavefront)
 //   write     four buffers per thread: out_off, out_cap, the status of the buffers at or behind the first one that does not fit, and the
@@ -28,33 +28,8 @@ __global__ void k_lay_result_init(u64* result, u32 words, u32 n, u32 skip)
     if (i < words && i != skip) result[i] = i == 1 ? n : 0;
 }
 
-__device__ __forceinline__ u64 wave_min(u64 v)
-{
-    for (u32 d = 32; d >= 1; d >>= 1) {
-        const u64 o = __shfl_xor(v, d, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ u64 wave_max(u64 v)
-{
-    for (u32 d = 32; d >= 1; d >>= 1) {
-        const u64 o = __shfl_xor(v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ u64 wave_sum(u64 v)
-{
-    for (u32 d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ void atomic_min64(u64* p, u64 v) { atomicMin(reinterpret_cast<unsigned long long*>(p), static_cast<unsigned long long>(v)); }
-__device__ __forceinline__ void atomic_max64(u64* p, u64 v) { atomicMax(reinterpret_cast<unsigned long long*>(p), static_cast<unsigned long long>(v)); }
-__device__ __forceinline__ void atomic_add64(u64* p, u64 v) { atomicAdd(reinterpret_cast<unsigned long long*>(p), static_cast<unsigned long long>(v)); }
-
 // ---- blocks ------------------------------------------------------------------------------------------------------------------------------------
-// snp_get_uncompressed_length (VarIntEncoding.TryReadSlow  VarIntEncoding.Read.cs:38-79) on at most 5 bytes, then scan_chunks' expansion rule
+// snp_get_uncompressed_length (VarIntEncoding.TryReadSlow  VarIntEncoding.Read.cs:38-79) on at most 5 bytes, then frame_hop's expansion rule
 __global__ __launch_bounds__(256) void k_bl_probe(const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len, u32 nb,
                                                  u32* __restrict__ declared, i32* __restrict__ status)
 {
@@ -66,7 +41,7 @@ __global__ __launch_bounds__(256) void k_bl_probe(const u8* __restrict__ in, con
     i32 st = SNP_ERR_BAD_LENGTH;
     u32 dec = 0;
     if (pre.end == SNP_PRE_DONE) {
-        // (a block that declares more can only end "Incomplete Snappy block.": capi_frame.hip scan_chunks)
+        // (a block that declares more can only end "Incomplete Snappy block.": frame_hop, frame_hop_device.h)
         const bool fits = pre.value <= snp_max_expansion(n - pre.bytes);
         st = fits ? SNP_OK : SNP_ERR_INCOMPLETE;
         dec = fits ? pre.value : 0;

@@ -62,6 +62,33 @@ __device__ __forceinline__ u32 read_lane(u32 v, u32 lane) { return __builtin_amd
 // 64-bit masks: lanes strictly below `lane`
 __device__ __forceinline__ u64 lanes_below(u32 lane) { return lane >= 64 ? ~0ull : ((1ull << lane) - 1ull); }
 
+// Reductions over the wavefront (every lane gets the result) and the 64-bit atomics that take it to a result word: the tails of the plan and
+// verdict kernels of the batch extension libraries ("one atomic per wavefront").  All lanes must call the reductions.
+__device__ __forceinline__ u64 wave_min(u64 v)
+{
+    for (u32 d = 32; d >= 1; d >>= 1) {
+        const u64 o = __shfl_xor(v, d, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ u64 wave_max(u64 v)
+{
+    for (u32 d = 32; d >= 1; d >>= 1) {
+        const u64 o = __shfl_xor(v, d, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ u64 wave_sum(u64 v)
+{
+    for (u32 d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ void atomic_min64(u64* p, u64 v) { atomicMin(reinterpret_cast<unsigned long long*>(p), static_cast<unsigned long long>(v)); }
+__device__ __forceinline__ void atomic_max64(u64* p, u64 v) { atomicMax(reinterpret_cast<unsigned long long*>(p), static_cast<unsigned long long>(v)); }
+__device__ __forceinline__ void atomic_add64(u64* p, u64 v) { atomicAdd(reinterpret_cast<unsigned long long*>(p), static_cast<unsigned long long>(v)); }
+
 // Wave-wide memcpy for a wave-uniform (dst, src, len): 16 B per lane per step while a full 1 KiB remains, then
 // 4 B per lane, then a byte tail.  src and dst must not overlap.  All lanes must call it.
 __device__ __forceinline__ void wave_copy(u8* dst, const u8* src, u32 len, u32 lane)

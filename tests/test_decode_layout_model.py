@@ -42,7 +42,7 @@ def test_extension_library_exports_exactly_its_header():
 
     ext = exported(N.LAYOUT_PATH)
     assert ext == set(NAMES)
-    for other in (N.PRODUCT_PATH, N.BUFFERS_PATH, N.BUFFERS_DECOMPRESS_PATH, N.FRAME_BUFFERS_PATH):
+    for other in (N.PRODUCT_PATH, N.BUFFERS_PATH, N.BUFFERS_DECOMPRESS_PATH, N.FRAME_BUFFERS_PATH, N.FRAME_RANGE_PATH):
         assert not exported(other) & ext
 
 
@@ -81,6 +81,17 @@ def test_workspace_sizes_of_the_four_extensions_are_pinned():
         assert F.snp_frame_decode_buffers_workspace(*args) == want, args
     for nb, want in {0: 0, 1: 512, 1000: 8448, 300000: 2402816}.items():
         assert Y.snp_decompress_layout_workspace(nb) == want, nb
+
+
+def test_workspace_sizes_of_the_framed_decode_calls_are_pinned():
+    """The same for the range decode's workspace, and for snp_frame_decode_workspace of the product library: a 64-byte header, the packed chunk
+    table of 37 bytes a row (two u64, five 32-bit words, one byte) rounded up to 16, and 16 bytes."""
+    from snappier_amd import _native as N
+    R, P = N.frame_range_lib(), N.lib()
+    for args, want in {(0, 0, 0, 0): 0, (1, 1, 1, 1): 12288, (1000, 70000, 5000, 1 << 20): 4893184, (163840, 163840, 163840, 0): 68325120}.items():
+        assert R.snp_frame_decode_range_workspace(*args) == want, args
+    for n, want in {0: 80, 1: 128, 8: 384, 163848: 6062464}.items():
+        assert P.snp_frame_decode_workspace(n) == want == 64 + (37 * n + 15) // 16 * 16 + 16, n
 
 
 def test_csharp_binding_matches_the_extension_header():

@@ -160,6 +160,20 @@ def hand_streams():
     return s
 
 
+def test_host_walk_equals_the_serial_walk():
+    """snp_frame_decoded_length (the host walk of capi_frame.hip) gives the status and the total of the model's serial walk on every hand stream
+    and on each of them cut short by 1 to 12 bytes: a cut inside the last header, CRC, preamble or body."""
+    import ctypes as C
+    from snappier_amd import _native as N
+    fn = N.lib().snp_frame_decoded_length
+    for name, x in hand_streams().items():
+        for cut in range(0, min(12, len(x)) + 1):
+            s = x[:len(x) - cut]
+            _rows, total, tail = M.serial_walk(s, cap=2 ** 63)
+            v = C.c_uint64(0)
+            assert (fn(s, len(s), C.byref(v)), v.value) == (tail, total), (name, cut)
+
+
 @pytest.mark.parametrize("span,window", [(256, 256), (256, 40), (333, 333), (1024, 200)])
 def test_span_walk_equals_the_serial_walk(span, window):
     for name, x in hand_streams().items():

@@ -877,6 +877,40 @@ def test_frame_decode_device_span_walk(scan):
     assert run(bytes(flipped))[1] == want
 
 
+@pytest.mark.parametrize("scan", [0, 1])
+def test_frame_decode_device_full_chunk_table(scan):
+    """A chunk table that fills up inside a span, in both header walks (SNP_OPT_FRAME_SCAN): five chunks of 1-7 raw bytes behind the stream
+    identifier and room for three rows -- the smallest shape at which a span's chunks overrun the table.  A failing chunk that was listed wins
+    over the full table (k_frame_result's precedence); one that was never listed is not seen.  0 bytes are reported on every failure."""
+    cd = SB.BlockCodec(0, O.HASH_CRC32C)
+    cd.ctx.set_option(N.OPT_FRAME_SCAN, scan)
+    raws = [bytes([65 + k]) * n for k, n in enumerate((1, 7, 3, 5, 2))]
+    chunks = [O.frame_encode(r)[10:] for r in raws]
+    good = O.frame_encode(b"")[:10] + b"".join(chunks)
+    at = [10 + sum(len(c) for c in chunks[:k]) for k in range(5)]      # position of every chunk header
+
+    def flipped(k):
+        b = bytearray(good)
+        b[at[k] + 4] ^= 1                                               # the stored CRC of chunk k
+        return bytes(b)
+
+    def run(stream, max_chunks):
+        fr = to_dev(np.frombuffer(stream, dtype=np.uint8))
+        out = torch.zeros(64, dtype=torch.uint8, device="cuda")
+        res = cd.frame_decode(fr, len(stream), out, max_chunks)
+        torch.cuda.synchronize()
+        written, status = (int(v) for v in res.cpu().tolist())
+        return status, written, out[:written].cpu().numpy().tobytes()
+
+    assert run(good, 3) == (O.ERR_OUTPUT_TOO_SMALL, 0, b"")
+    assert run(flipped(1), 3) == (O.ERR_CRC_MISMATCH, 0, b"")
+    assert run(flipped(4), 3) == (O.ERR_OUTPUT_TOO_SMALL, 0, b"")
+    assert run(good, 5) == (O.OK, 18, b"".join(raws))
+    assert run(flipped(1), 5) == (O.ERR_CRC_MISMATCH, 0, b"")
+    assert run(flipped(4), 5) == (O.ERR_CRC_MISMATCH, 0, b"")
+    cd.ctx.close()
+
+
 # ------------------------------------------------------------------ full BASELINE size, size-independent properties
 
 @pytest.mark.timeout(1200)
