@@ -162,6 +162,13 @@ _EXTENSIONS = {
     "frame_range": ("libsnappier_hip_frame_range.so", "snappier_hip_frame_range.h", {
         "snp_frame_decode_range_workspace": (_u64, [_u32, _u32, _u32, _u64]),
         "snp_frame_decode_range_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device seek index for framed streams and indexed window reads: any number of windows, each naming a stream, with no header walk
+    "frame_index": ("libsnappier_hip_frame_index.so", "snappier_hip_frame_index.h", {
+        "snp_frame_index_workspace": (_u64, [_u32, _u32]),
+        "snp_frame_index_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "snp_frame_read_indexed_workspace": (_u64, [_u32, _u32, _u64]),
+        "snp_frame_read_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u32, _u64,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -201,6 +208,7 @@ BUFFERS_DECOMPRESS_PATH = _extension_path("buffers_decompress")
 FRAME_BUFFERS_PATH = _extension_path("frame_buffers")
 LAYOUT_PATH = _extension_path("layout")
 FRAME_RANGE_PATH = _extension_path("frame_range")
+FRAME_INDEX_PATH = _extension_path("frame_index")
 
 
 def buffers_lib() -> C.CDLL:
@@ -228,6 +236,11 @@ def frame_range_lib() -> C.CDLL:
     return _extension("frame_range")
 
 
+def frame_index_lib() -> C.CDLL:
+    """libsnappier_hip_frame_index.so (include/snappier_hip_frame_index.h)."""
+    return _extension("frame_index")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -246,6 +259,10 @@ def layout_declared_symbols() -> list[str]:
 
 def frame_range_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_range"))
+
+
+def frame_index_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_index"))
 
 
 def status_string(st: int) -> str:

@@ -408,6 +408,114 @@ class BlockCodec:
                                                              max_chunks=min(need[0], 0xFFFFFFFF), max_spans=spans, edge_cap=need[4])
         return out[:need[-1]], out_off, out_len, status
 
+    def frame_index_buffers(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, max_spans: int | None = None,
+                            max_entries: int | None = None, work: torch.Tensor | None = None) -> "FrameIndex":
+        """The chunk index of many framed streams, walked once (snp_frame_index_batch, libsnappier_hip_frame_index.so): -> FrameIndex.
+
+        Stream b is framed[in_off[b] .. +in_len[b]).  The index holds one row per data chunk (the decoded bytes before it and where its header
+        is, relative to the stream's first byte), each stream's decoded length and the status of its header walk; frame_read_indexed and
+        frame_gather_to_memory read any number of windows through it with no header walk, and it stays valid when the framed bytes move.
+        index.result is the 4-element int64 d_result: [0] = rows needed, [1] = decoded bytes of the indexed streams, [2] = span slots needed,
+        [3] = spans the resolver walked on the spot.  Default max_spans: EXACT (sum of ceil(in_len / 2^20)), ONE synchronising read-back.
+        Default max_entries: a first call with max_entries = 0 (it walks every stream and writes no row), then a synchronising read of its
+        d_result[0].  A caller that passes max_spans, max_entries and work enqueues only."""
+        self._bind()
+        ns = in_len.numel()
+        IL = N.frame_index_lib()
+        if max_spans is None:
+            n = in_len.to(torch.int64)
+            max_spans = int(((n + (1 << 20) - 1) >> 20).sum().item()) if ns else 0
+        framed = self._readable(framed, ns)
+        first = torch.zeros(ns + 1, dtype=torch.int64, device=self.device)
+        total = torch.empty(ns, dtype=torch.int64, device=self.device)
+        tail = torch.empty(ns, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+
+        def call(me: int, w: torch.Tensor | None):
+            w = self._work("frame_index_buffers", w, IL.snp_frame_index_workspace, ns, max_spans)
+            start = torch.empty(max(me, 1), dtype=torch.int64, device=self.device)
+            pos = torch.empty(max(me, 1), dtype=torch.int64, device=self.device)
+            st = IL.snp_frame_index_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, max_spans, me, _p(first), _p(start), _p(pos),
+                                          _p(total), _p(tail), _p(w), _p(result))
+            raise_for_status(st, self.ctx.handle)
+            return start[:me], pos[:me]
+
+        if max_entries is None:
+            call(0, work)
+            max_entries = int(result[0].item())
+        start, pos = call(max_entries, work)
+        return FrameIndex(first, start, pos, total, tail, result)
+
+    def frame_read_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", req_stream: torch.Tensor,
+                           req_off: torch.Tensor, req_len: torch.Tensor, out: torch.Tensor, out_off: torch.Tensor, out_cap: torch.Tensor,
+                           max_chunks: int | None = None, edge_cap: int | None = None, work: torch.Tensor | None = None):
+        """Any number of windows, each naming a stream, read through a chunk index with no header walk (snp_frame_read_indexed_batch,
+        libsnappier_hip_frame_index.so): -> (out_len, status, result).
+
+        Request r reads bytes [req_off[r], req_off[r] + req_len[r]) of what stream req_stream[r] (int32) decodes to into
+        out[out_off[r] .. +out_cap[r]) (int64 tensors, read as unsigned); status / out_len are what frame_decode_range_buffers gives for that
+        stream alone with that window.  Requests are independent; many may name one stream.  The index is checked against the framed bytes
+        row by row: a stale or foreign one gives SNP_ERR_BAD_ARG per request (include/snappier_hip_frame_index.h).  result is the 4-element
+        int64 d_result: [0] = interior chunk slots needed, [1] = sum of out_len over the OK requests, [2] = edge scratch bytes needed, [3] =
+        requests that are OK.  Default max_chunks and edge_cap: a first call with both 0 (it plans and decodes nothing), then a synchronising
+        read of its d_result.  A caller that passes max_chunks, edge_cap and work enqueues only."""
+        self._bind()
+        nreq, ns = req_stream.numel(), in_len.numel()
+        if req_stream.dtype != torch.int32:
+            raise ValueError("frame_read_indexed: req_stream must be an int32 tensor")
+        IL = N.frame_index_lib()
+        framed, out = self._readable(framed, nreq), self._readable(out, nreq)
+        out_len = torch.empty(nreq, dtype=torch.int64, device=self.device)
+        status = torch.empty(nreq, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+
+        def call(mc: int, ec: int, w: torch.Tensor | None):
+            w = self._work("frame_read_indexed", w, IL.snp_frame_read_indexed_workspace, nreq, mc, ec)
+            st = IL.snp_frame_read_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                                 _p(index.total), _p(index.tail), index.nentries, _p(req_stream), _p(req_off), _p(req_len), nreq,
+                                                 mc, ec, _p(out), _p(out_off), _p(out_cap), _p(out_len), _p(status), _p(w), _p(result))
+            raise_for_status(st, self.ctx.handle)
+
+        if max_chunks is None or edge_cap is None:
+            call(0, 0, None)
+            need = result.tolist()
+            max_chunks = min(need[0], 0xFFFFFFFF) if max_chunks is None else max_chunks
+            edge_cap = need[2] if edge_cap is None else edge_cap
+        call(max_chunks, edge_cap, work)
+        return out_len, status, result
+
+    def frame_gather_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", req_stream: torch.Tensor,
+                               req_off: torch.Tensor, req_len: torch.Tensor, align: int = 1, max_bytes: int | None = None):
+        """Read any number of windows given the framed tensor, its table, its index and the requests: -> (out, out_off, out_len, status).
+
+        The counterpart of frame_read_to_memory.  Windows are clipped to the stream, so req_len[r] bounds what request r delivers; so does
+        22 x in_len of its stream (no chunk decodes to more).  Request r's slot is the smaller of the two rounded up to `align`, out_off[r] the
+        sum of the slots before it.  ONE sizing call (max_chunks = edge_cap = 0) with ONE synchronising read of its result and of the arena
+        size (ValueError if that is above max_bytes), then the read."""
+        nreq, ns = req_stream.numel(), in_len.numel()
+        empty = torch.empty(0, dtype=torch.uint8, device=self.device)
+        if nreq == 0:
+            z = torch.empty(0, dtype=torch.int64, device=self.device)
+            return empty, z, z.clone(), torch.empty(0, dtype=torch.int32, device=self.device)
+        rl = req_len.to(torch.int64)
+        rs = req_stream.to(torch.int64)
+        known = (rs >= 0) & (rs < ns)
+        lens = in_len.to(torch.int64)[torch.where(known, rs, torch.zeros_like(rs))] if ns else torch.zeros_like(rs)
+        bound = torch.where(known, lens * 22, torch.zeros_like(rs))       # (a request on no stream of the batch delivers nothing)
+        out_cap = torch.where((rl < 0) | (rl > bound), bound, rl)            # (a negative int64 is a length of 2^63 or more)
+        slot = (out_cap + (align - 1)) // align * align
+        ends = torch.cumsum(slot, 0)
+        out_off = ends - slot
+        _, _, result = self.frame_read_indexed(framed, in_off, in_len, index, req_stream, req_off, req_len, empty, out_off, out_cap, 0, 0)
+        need = torch.cat([result, ends[-1:]]).tolist()
+        if max_bytes is not None and need[-1] > max_bytes:
+            raise ValueError(f"frame_gather_to_memory: the windows take {need[-1]} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need[-1], 1), dtype=torch.uint8, device=self.device)
+        out_len, status, _ = self.frame_read_indexed(framed, in_off, in_len, index, req_stream, req_off, req_len, out, out_off, out_cap,
+                                                     max_chunks=min(need[0], 0xFFFFFFFF), edge_cap=need[2])
+        return out[:need[-1]], out_off, out_len, status
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()
@@ -432,3 +540,19 @@ class BlockCodec:
         st = self.ctx.lib.snp_frame_decode_device(self.ctx.handle, _p(framed), nbytes, _p(out), out.numel(), max_chunks, _p(work), _p(result))
         raise_for_status(st, self.ctx.handle)
         return result
+
+
+class FrameIndex:
+    """The chunk index of a batch of framed streams (BlockCodec.frame_index_buffers; include/snappier_hip_frame_index.h): five device tensors --
+    first (int64, nstreams + 1), start and pos (int64, one per row), total (int64) and tail (int32) per stream -- and the d_result of the call
+    that built it.  It names no address: it is valid for the same streams wherever they lie, and may be stored and loaded again."""
+
+    def __init__(self, first: torch.Tensor, start: torch.Tensor, pos: torch.Tensor, total: torch.Tensor, tail: torch.Tensor,
+                 result: torch.Tensor | None = None):
+        self.first, self.start, self.pos, self.total, self.tail, self.result = first, start, pos, total, tail, result
+
+    @property
+    def nentries(self) -> int:
+        """Rows the start / pos tensors hold."""
+        return min(self.start.numel(), self.pos.numel())
+

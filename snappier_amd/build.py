@@ -1,7 +1,8 @@
 """Builds the gfx950 native libraries in-tree with hipcc (cross-compiles without a GPU).
 
     python snappier_amd/build.py            # libsnappier_hip.so, libsnappier_hip_buffers.so, libsnappier_hip_buffers_decompress.so,
-                                            # libsnappier_hip_frame_buffers.so, libsnappier_hip_layout.so, libsnappier_hip_frame_range.so
+                                            # libsnappier_hip_frame_buffers.so, libsnappier_hip_layout.so, libsnappier_hip_frame_range.so,
+                                            # libsnappier_hip_frame_index.so
                                             # (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
@@ -29,6 +30,8 @@ LIBS = {
     "libsnappier_hip_layout.so": ["layout.hip"],
     # include/snappier_hip_frame_range.h: device batch range decode of framed streams (a window of every stream) -- the same kind of extension
     "libsnappier_hip_frame_range.so": ["frame_range.hip"],
+    # include/snappier_hip_frame_index.h: device seek index for framed streams and indexed window reads -- the same kind of extension
+    "libsnappier_hip_frame_index.so": ["frame_index.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 # every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)

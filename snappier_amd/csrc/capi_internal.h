@@ -5,10 +5,11 @@
 //     capi_batch.hip   launch policy of the device-pointer batch entry points (which kernel for which batch), snp_*_batch
 //     capi_host.hip    the host-pointer calls: snp_try_compress / snp_try_decompress (+ segments), snp_crc32c
 //     capi_frame.hip   framing orchestration: snp_frame_encode* / snp_frame_decode*, the host header walk, snp_ctx::decode_chunks
-// The batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip, frame_range.hip: one file and one header under include/ each)
+// The batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip, frame_range.hip, frame_index.hip: one file and one header under include/ each)
 // are linked against libsnappier_hip.so and drive its contexts through this header; what they share among themselves is in work_carver.h,
 // scan_tiles.h, frame_hop_device.h (one hop of a framed stream's header walk, the per-span bodies, the span and chunk tables: shared with framing.hip,
-// frame_scan.hip and capi_frame.hip) and frame_walk_device.h (the span walk over many streams).
+// frame_scan.hip and capi_frame.hip), frame_walk_device.h (the span walk over many streams), frame_edges_device.h (the edge chunks of a window:
+// range decode and indexed read) and frame_index_device.h (the planning of one indexed request, host and device).
 // No codec arithmetic happens on the host: every byte of compress / decompress / CRC work is done by the gfx950 kernels in compress_lanes.hip,
 // compress_win.hip, decode_chains.hip, decompress.hip, decompress_small.hip, tag_index.hip, crc32c.hip, framing.hip, frame_scan.hip.
 // There is no CPU fallback -- without a HIP device snp_ctx_create fails with SNP_ERR_DEVICE.
@@ -29,7 +30,7 @@
 #include "snp_rules.h"
 
 // The chunk table of a framed decode, structure of arrays over n rows: what the header walks write (frame_hop_device.h) and the decoder and the
-// CRC verify read (snp_ctx::decode_chunks).  tag: the row's stream in the batch and range tables (`owner`), its edge slot in the range call's edge
+// CRC verify read (snp_ctx::decode_chunks).  tag: the row's stream in the batch and range tables (`owner`), its request in the indexed read's, its edge slot in the range call's and the indexed read's edge
 // table (`src`), kNone for an empty row; the one-stream table has none (nullptr).
 struct ChunkRows {
     u8* type;

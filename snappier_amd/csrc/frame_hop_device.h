@@ -4,7 +4,7 @@
 // span's entry among the candidates of 64 spans (walk B), the hops over a span's data chunks from its entry (walk C) and the empty row.  Its users
 // are thin drivers that find their stream and span: the one-stream walks (framing.hip k_frame_scan, frame_scan.hip k_span_*:
 // snp_frame_decode_device), the many-stream walk (frame_walk_device.h k_fd_candidates, k_fd_resolve) and the kernels behind it (frame_buffers.hip,
-// frame_range.hip).  What belongs to MANY streams -- the per-stream record, the span slots of a batch, the launches -- is frame_walk_device.h.
+// frame_range.hip, frame_index.hip) and the row check of the indexed read (frame_index_device.h, which calls frame_hop on the host too).  What belongs to MANY streams -- the per-stream record, the span slots of a batch, the launches -- is frame_walk_device.h.
 // The block preamble and the expansion bound inside a hop are snp_rules.h's.
 #pragma once
 #include "snp_rules.h"

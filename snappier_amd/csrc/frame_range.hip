@@ -25,13 +25,13 @@
 // Nothing here allocates, reads back or synchronises: the call is capturable like the other _batch entry points.
 #include "capi_internal.h"
 #include "frame_walk_device.h"
+#include "frame_edges_device.h"
 #include "../../include/snappier_hip_frame_range.h"
 
 namespace {
 
 constexpr u32 kSmall = 1u;              // flags: hi - lo > out_cap (nothing of the stream is selected)
 constexpr u32 kAdmitted = 2u;           // flags: spans, interior rows and edge bytes fit
-constexpr u64 kNoFail = ~0ull;
 
 // per stream
 struct FrStreams {
@@ -39,12 +39,7 @@ struct FrStreams {
     u32* flags;
     u64* fail;          // min over the failing interior rows of (1 + place among the stream's rows) << 8 | status
 };
-// two edge slots per stream, where k_fr_select records what it finds (head: 2 b, tail: 2 b + 1); dec == 0: an empty slot
-struct FrEdges {
-    u8* type;
-    u64 *body_off, *start, *place, *rank;   // start: s, the chunk's first decoded byte in its stream; place, rank: the scans of dec and of dec != 0 (2 ns + 1 each)
-    u32 *body_len, *crc, *dec;
-};
+// Two edge slots per stream (FrEdges, frame_edges_device.h), where k_fr_select records what it finds (head: 2 b, tail: 2 b + 1).
 // The two chunk tables (ChunkRows): the interior rows over max_chunks slots, tagged with their stream; and the edge table the decoder sees, 2 ns
 // rows -- the edges of the admitted streams in stream order, then empty rows -- tagged with the edge slot the row came from.
 
@@ -103,13 +98,7 @@ __global__ __launch_bounds__(SNP_WAVE) void k_fr_select(const u8* __restrict__ i
                                         if (off >= lo && off + h.dec <= hi) {
                                             ++cnt;
                                         } else {                        // an edge: the one chunk that holds lo is the head, any other the tail
-                                            const u64 slot = 2ull * b + (off > lo ? 1 : 0);
-                                            e.type[slot] = static_cast<u8>(h.type);
-                                            e.body_off[slot] = ib + ip + SNP_CHUNK_HEADER_LEN;
-                                            e.body_len[slot] = h.body_len;
-                                            e.crc[slot] = h.crc;
-                                            e.dec[slot] = h.dec;
-                                            e.start[slot] = off;
+                                            edge_slot_set(e, 2ull * b + (off > lo ? 1 : 0), h, ib + ip, off);
                                         }
                                     }
                                     return off + h.dec < hi;            // the chunks behind the window are not hopped
@@ -119,15 +108,6 @@ __global__ __launch_bounds__(SNP_WAVE) void k_fr_select(const u8* __restrict__ i
     }
     icount[g] = cnt;
 }
-
-struct ScanEdgeBytes {
-    const u32* __restrict__ dec;
-    __device__ __forceinline__ u64 operator()(u64 i) const { return dec[i]; }
-};
-struct ScanEdgeCount {
-    const u32* __restrict__ dec;
-    __device__ __forceinline__ u64 operator()(u64 i) const { return dec[i] != 0; }
-};
 
 // Admission (in stream order: the three sums only grow), the rows of the admitted streams' edges with their places in the scratch arena,
 // d_result[4] and [5].  (A rank is below 2 ns and belongs to one edge: every row is written by one thread, after k_fr_window emptied it.)
@@ -142,15 +122,7 @@ __global__ __launch_bounds__(256) void k_fr_admit(u32 ns, const u64* __restrict_
         for (u64 slot = 2ull * b; slot < 2ull * b + 2; ++slot) {
             if (e.dec[slot] == 0) continue;
             ++nsel;
-            if (!ok) continue;
-            const u64 row = e.rank[slot];
-            c.tag[row] = static_cast<u32>(slot);
-            c.type[row] = e.type[slot];
-            c.body_off[row] = e.body_off[slot];
-            c.body_len[row] = e.body_len[slot];
-            c.crc[row] = e.crc[slot];
-            c.out_off[row] = e.place[slot];
-            c.out_cap[row] = e.dec[slot];
+            if (ok) edge_row_place(c, e, slot);
         }
         if (b == 0) {
             result[4] = e.place[2ull * ns];
@@ -197,21 +169,15 @@ __global__ __launch_bounds__(SNP_WAVE) void k_fr_emit(const u8* __restrict__ in,
                     });
 }
 
-// One workgroup per edge row: an OK edge's bytes inside the window, scratch -> out.  (A row in use belongs to an admitted stream whose window
-// fits its out_cap: max(s, lo) - lo + the bytes copied = min(s + d, hi) - lo <= hi - lo <= out_cap.)
+// One workgroup per edge row: an OK edge's bytes inside the window, scratch -> out (edge_trim).
 __global__ __launch_bounds__(256) void k_fr_trim(ChunkRows c, FrEdges e, FrStreams w, const u8* __restrict__ scratch, u8* __restrict__ out,
                                                 const u64* __restrict__ out_off)
 {
     const u64 row = blockIdx.x;
     const u32 slot = c.tag[row];
     if (slot == kNone) return;
-    const u32 d = c.out_cap[row];
-    if (c.status[row] != SNP_OK || c.out_len[row] != d) return;
     const u32 b = slot >> 1;
-    const u64 lo = w.lo[b], hi = w.hi[b], s = e.start[slot];
-    const u64 from = s > lo ? s : lo, to = s + d < hi ? s + d : hi;
-    if (to <= from) return;
-    block_copy(out + out_off[b] + (from - lo), scratch + c.out_off[row] + (from - s), static_cast<u32>(to - from), threadIdx.x);
+    edge_trim(c, e, row, slot, w.lo[b], w.hi[b], scratch, out + out_off[b], threadIdx.x);
 }
 
 // k_fd_fail over the interior table, keyed by the row's place in its stream
@@ -221,8 +187,7 @@ __global__ __launch_bounds__(256) void k_fr_fail(u32 max_chunks, ChunkRows r, co
     if (c >= max_chunks) return;
     const u32 b = r.tag[c];
     if (b == kNone || r.status[c] == SNP_OK) return;
-    const u64 key = ((1 + (c - ispan[sfirst[b]])) << 8) | static_cast<u64>(r.status[c] & 0xff);
-    atomicMin(reinterpret_cast<unsigned long long*>(w.fail + b), static_cast<unsigned long long>(key));
+    atomic_min64(w.fail + b, fail_key(c - ispan[sfirst[b]], r.status[c]));
 }
 
 // the stream's verdict: the first failing selected chunk in stream order (head edge, interior rows, tail edge), else the error that ended the
@@ -236,13 +201,8 @@ __global__ __launch_bounds__(256) void k_fr_verdict(u32 ns, FbStreams st, FrStre
         i32 s = SNP_ERR_OUTPUT_TOO_SMALL;
         const u32 flags = w.flags[b];
         if (flags & kAdmitted) {
-            const u64 head = 2ull * b, tail = head + 1, f = w.fail[b];
-            const i32 s_head = e.dec[head] ? c.status[e.rank[head]] : SNP_OK, s_tail = e.dec[tail] ? c.status[e.rank[tail]] : SNP_OK;
-            if (s_head != SNP_OK) s = s_head;
-            else if (f != kNoFail) s = static_cast<i32>(f & 0xff);
-            else if (s_tail != SNP_OK) s = s_tail;
-            else if (st.tail[b] != SNP_OK) s = st.tail[b];
-            else if (!(flags & kSmall)) { s = SNP_OK; ok_len = w.hi[b] - w.lo[b]; }
+            s = window_verdict(edge_status(c, e, 2ull * b), w.fail[b], edge_status(c, e, 2ull * b + 1), st.tail[b], flags & kSmall);
+            if (s == SNP_OK) ok_len = w.hi[b] - w.lo[b];
         }
         status[b] = s;
         out_len[b] = ok_len;
@@ -283,14 +243,7 @@ RangeWork range_work_layout(void* base, u32 nstreams, u32 max_chunks, u32 max_sp
     k.icount = c.take<u32>(nsp);
     k.ispan = c.take<u64>(nsp + 1);
     k.r = carve_chunk_rows(c, nc);
-    k.e.body_off = c.take<u64>(ne);
-    k.e.start = c.take<u64>(ne);
-    k.e.place = c.take<u64>(ne + 1);
-    k.e.rank = c.take<u64>(ne + 1);
-    k.e.body_len = c.take<u32>(ne);
-    k.e.crc = c.take<u32>(ne);
-    k.e.dec = c.take<u32>(ne);
-    k.e.type = c.take<u8>(ne);
+    k.e = carve_edges(c, ne);
     k.c = carve_chunk_rows(c, ne);
     k.scratch = c.take<u8>(edge_cap);
     k.bytes = c.bytes();

@@ -3,7 +3,7 @@
 // (k_fd_candidates) and walk B (k_fd_resolve) with their launch (launch_span_walk).  What one span of one stream takes -- the hop, the candidates,
 // the lookup among them, the span and chunk tables -- is frame_hop_device.h; the drivers here only find their stream and span slot.  Shared by the
 // batch decode (frame_buffers.hip, snp_frame_decode_buffers_batch), the decode layout (layout.hip, snp_frame_decode_layout_batch) and the range
-// decode (frame_range.hip, snp_frame_decode_range_batch); the resolver takes out_cap == nullptr as "no bound" (the layout call asks for the totals,
+// decode (frame_range.hip, snp_frame_decode_range_batch) and the index build (frame_index.hip, snp_frame_index_batch); the resolver takes out_cap == nullptr as "no bound" (the layout call asks for the totals,
 // it has no capacities yet).
 #pragma once
 #include "scan_tiles.h"

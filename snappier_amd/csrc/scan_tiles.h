@@ -1,5 +1,5 @@
 // scan_tiles.h -- exclusive prefix sums of u64 values over up to 2^32 positions, reduce-then-scan across workgroups (tiles of SNP_SCAN_TILE values):
-// the plan scans of the batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip, frame_range.hip), and owner_of, their inverse.  What is scanned is a functor V: V(i) = the value at position i, so a scan
+// the plan scans of the batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip, frame_range.hip, frame_index.hip), and owner_of, their inverse.  What is scanned is a functor V: V(i) = the value at position i, so a scan
 // reads its source as the caller's kernels see it (fragments of a length, a masked length, a packed pair of counts) with no array in between.
 // Three launches; the partial array holds one tile sum per tile (+ 1), dst holds n + 1 values (dst[n] = the grand total).
 #pragma once
