@@ -10,7 +10,7 @@ COMPRESS_LAYOUTS = ["win", "win-np2", "wing", "wind", "lanes", "lanes-exact", "l
                     "lanes-opts151-slots2", "lanes-per16", "lanes-slots4"]
 # chains = the default (decode_chains.hip after the small-block policy); wave-only = no pre-pass; serial = decompress.hip's tag-by-tag kernel;
 # small* = every block through the small-block pre-pass first (decompress_small.hip), leftovers to the list kernel (or one workgroup each: -grid)
-DECODE_LAYOUTS = ["chains", "wave-only", "serial", "small", "small-grid", "small-lanes", "small-team4", "small-team16"]
+DECODE_LAYOUTS = ["chains", "wave-only", "serial", "small", "small-grid", "small-lanes", "small-team4", "small-team8", "small-team16"]
 
 
 def set_compress_layout(ctx, layout: str):
