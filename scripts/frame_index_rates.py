@@ -11,7 +11,7 @@ ms from HIP events around each call (median of --reps after one warm-up); every 
 measurement to --out.  The lines of the 64 MiB shape carry the condition the index rests on, for both 1 MiB windows and the 4 KiB window:
 indexed read < range call - 1/2 x (range sizing call alone), all three measured in this run.
 
-    python scripts/frame_index_rates.py --out profiles/r11a_frame_index_rates.jsonl
+    python scripts/frame_index_rates.py --out profiles/r12a_frame_index_rates.jsonl
 """
 import argparse
 import json

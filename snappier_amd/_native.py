@@ -169,6 +169,10 @@ _EXTENSIONS = {
         "snp_frame_read_indexed_workspace": (_u64, [_u32, _u32, _u64]),
         "snp_frame_read_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u32, _u64,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch frame encode with a chosen chunk size, and the seek index of what it wrote
+    "frame_chunked": ("libsnappier_hip_frame_chunked.so", "snappier_hip_frame_chunked.h", {
+        "snp_frame_encode_chunked_workspace": (_u64, [_u32, _u32, _u32]),
+        "snp_frame_encode_chunked_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -209,6 +213,7 @@ FRAME_BUFFERS_PATH = _extension_path("frame_buffers")
 LAYOUT_PATH = _extension_path("layout")
 FRAME_RANGE_PATH = _extension_path("frame_range")
 FRAME_INDEX_PATH = _extension_path("frame_index")
+FRAME_CHUNKED_PATH = _extension_path("frame_chunked")
 
 
 def buffers_lib() -> C.CDLL:
@@ -241,6 +246,11 @@ def frame_index_lib() -> C.CDLL:
     return _extension("frame_index")
 
 
+def frame_chunked_lib() -> C.CDLL:
+    """libsnappier_hip_frame_chunked.so (include/snappier_hip_frame_chunked.h)."""
+    return _extension("frame_chunked")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -263,6 +273,10 @@ def frame_range_declared_symbols() -> list[str]:
 
 def frame_index_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_index"))
+
+
+def frame_chunked_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_chunked"))
 
 
 def status_string(st: int) -> str:

@@ -252,6 +252,56 @@ class BlockCodec:
         raise_for_status(st, self.ctx.handle)
         return out, out_off, out_len, status, result
 
+    def frame_encode_seekable(self, data: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, chunk_bytes: int = N.BLOCK_SIZE,
+                              with_index: bool = True, out: torch.Tensor | None = None, out_off: torch.Tensor | None = None,
+                              out_cap: torch.Tensor | None = None, max_chunks: int | None = None, work: torch.Tensor | None = None):
+        """Many framed streams in one call with a chosen chunk size, and their seek index (snp_frame_encode_chunked_batch,
+        libsnappier_hip_frame_chunked.so): -> (out, out_off, out_len, status, result, FrameIndex | None).
+
+        frame_encode_buffers with one chunk per chunk_bytes (1 .. 65536) input bytes instead of per 65536: the chunk is what a window read
+        decodes whole, so a caller who reads small records picks a small chunk and pays for it in compressed size.  Defaults: out_cap =
+        10 + 8 * ceil(n / chunk_bytes) + n per buffer, out_off = its exclusive cumsum, out sized to the sum, and max_chunks EXACT (sum of
+        ceil(n / chunk_bytes)).  Any default among out, max_chunks and work costs ONE synchronising read-back; a caller that passes all three
+        -- and out_off / out_cap -- enqueues only.  result is the 4-element int64 d_result: [0] = chunk slots the batch needs, [1] = sum of
+        out_len over the OK buffers, [2] = index rows written, [3] = buffers that are OK.  With with_index the returned FrameIndex (its start /
+        pos hold max_chunks rows) is what frame_index_buffers gives for the emitted streams, with no header walk, and goes straight into
+        frame_read_indexed / frame_gather_to_memory with (out, out_off, out_len) as the framed streams."""
+        if not 1 <= chunk_bytes <= N.BLOCK_SIZE:
+            raise ValueError(f"frame_encode_seekable: chunk_bytes = {chunk_bytes}, must be 1 .. {N.BLOCK_SIZE}")
+        self._bind()
+        nb = in_len.numel()
+        n = in_len.to(torch.int64)
+        chunks = (n + chunk_bytes - 1) // chunk_bytes
+        if out_cap is None:
+            out_cap = 10 + 8 * chunks + n
+        if out_off is None:
+            out_off = torch.cumsum(out_cap, 0) - out_cap
+        if out is None or max_chunks is None:
+            sums = torch.stack([(out_off + out_cap).max() if nb else n.new_zeros(()), chunks.sum()]).tolist()
+            if out is None:
+                out = torch.empty(max(int(sums[0]), 1), dtype=torch.uint8, device=self.device)
+            if max_chunks is None:
+                max_chunks = int(sums[1])
+        CL = N.frame_chunked_lib()
+        work = self._work("frame_encode_seekable", work, CL.snp_frame_encode_chunked_workspace, nb, max_chunks, chunk_bytes)
+        data = self._readable(data, nb)
+        out_len = torch.empty(nb, dtype=torch.int64, device=self.device)
+        status = torch.empty(nb, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        index, ix = None, [None] * 5
+        if with_index:
+            first = torch.zeros(nb + 1, dtype=torch.int64, device=self.device)
+            start = torch.empty(max(max_chunks, 1), dtype=torch.int64, device=self.device)
+            pos = torch.empty(max(max_chunks, 1), dtype=torch.int64, device=self.device)
+            total = torch.empty(max(nb, 1), dtype=torch.int64, device=self.device)
+            tail = torch.empty(max(nb, 1), dtype=torch.int32, device=self.device)
+            ix = [first, start, pos, total, tail]
+            index = FrameIndex(first, start[:max_chunks], pos[:max_chunks], total[:nb], tail[:nb], result)
+        st = CL.snp_frame_encode_chunked_batch(self.ctx.handle, _p(data), _p(in_off), _p(in_len), nb, chunk_bytes, max_chunks, _p(out), _p(out_off),
+                                               _p(out_cap), _p(out_len), _p(status), *[_p(t) for t in ix], _p(work), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return out, out_off, out_len, status, result, index
+
     def frame_decode_buffers(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, out: torch.Tensor, out_off: torch.Tensor,
                              out_cap: torch.Tensor, max_chunks: int | None = None, max_spans: int | None = None, work: torch.Tensor | None = None):
         """Many framed streams in one call (snp_frame_decode_buffers_batch, libsnappier_hip_frame_buffers.so): -> (out_len, status, result).

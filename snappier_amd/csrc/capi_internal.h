@@ -5,11 +5,12 @@
 //     capi_batch.hip   launch policy of the device-pointer batch entry points (which kernel for which batch), snp_*_batch
 //     capi_host.hip    the host-pointer calls: snp_try_compress / snp_try_decompress (+ segments), snp_crc32c
 //     capi_frame.hip   framing orchestration: snp_frame_encode* / snp_frame_decode*, the host header walk, snp_ctx::decode_chunks
-// The batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip, frame_range.hip, frame_index.hip: one file and one header under include/ each)
+// The batch extension libraries (buffers.hip, buffers_decode.hip, frame_buffers.hip, layout.hip, frame_range.hip, frame_index.hip, frame_chunked.hip: one file and one header under include/ each)
 // are linked against libsnappier_hip.so and drive its contexts through this header; what they share among themselves is in work_carver.h,
 // scan_tiles.h, frame_hop_device.h (one hop of a framed stream's header walk, the per-span bodies, the span and chunk tables: shared with framing.hip,
 // frame_scan.hip and capi_frame.hip), frame_walk_device.h (the span walk over many streams), frame_edges_device.h (the edge chunks of a window:
-// range decode and indexed read) and frame_index_device.h (the planning of one indexed request, host and device).
+// range decode and indexed read), frame_index_device.h (the planning of one indexed request, host and device) and frame_chunked_device.h (the slot
+// arithmetic of the chunked frame encode, host and device).
 // No codec arithmetic happens on the host: every byte of compress / decompress / CRC work is done by the gfx950 kernels in compress_lanes.hip,
 // compress_win.hip, decode_chains.hip, decompress.hip, decompress_small.hip, tag_index.hip, crc32c.hip, framing.hip, frame_scan.hip.
 // There is no CPU fallback -- without a HIP device snp_ctx_create fails with SNP_ERR_DEVICE.
@@ -78,7 +79,12 @@ hipError_t snp_launch_frame_emit(const u8*, const u64*, const u8*, const u64*, c
                                  const u64*, u8*, u64, u32, hipStream_t);
 }
 
-constexpr u64 kSnpCompStride = 76496 + 16;   // snp_max_compressed_length(65536), padded to a 16-byte multiple
+// Staging stride of one compressed fragment of at most n bytes: snp_max_compressed_length(n) = 38 + n + n / 6 rounded up to 16, plus 16.  Every
+// store of the three compressors stays inside snp_max_compressed_length of the fragment it compresses, whatever its length (checked in
+// DESIGN.md 4.15), so the 16 bytes are slack that nothing writes.
+constexpr u64 snp_comp_stride(u64 n) { return (38 + n + n / 6 + 15) / 16 * 16 + 16; }
+constexpr u64 kSnpCompStride = snp_comp_stride(SNP_BLOCK_SIZE);   // snp_max_compressed_length(65536), padded to a 16-byte multiple, + 16
+static_assert(kSnpCompStride == 76496 + 16, "staging stride of a 64 KiB fragment");
 
 struct DevBuf {
     void* p = nullptr;
