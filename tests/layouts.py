@@ -8,6 +8,12 @@ from snappier_amd import _native as N
 
 COMPRESS_LAYOUTS = ["win", "win-np2", "wing", "wind", "lanes", "lanes-exact", "lanes-opts7", "lanes-opts31", "lanes-opts87-slots1", "lanes-opts215-slots1",
                     "lanes-opts151-slots2", "lanes-per16", "lanes-slots4"]
+# The four launch forms snp_launch_compress_lanes picks from the batch size (stores | probes per trip | fragments per wavefront), selectable here on
+# a batch of any size, and the one remaining wavefront filling: below 8 192 fragments, 8 192 .. 32 767, 32 768 .. 131 071, from 131 072.
+# KEPT IN STEP BY HAND with the policy at snappier_amd/csrc/compress_lanes.hip:725-747 (per / opts / slots): when a threshold or a default there
+# changes, change these names with it -- nothing derives them from the kernel.
+COMPRESS_TIERS = ["lanes-opts71-slots2-per16", "lanes-opts71-slots2-per32", "lanes-opts87-slots2-per32", "lanes-opts215-slots1-per64"]
+COMPRESS_LAYOUTS += COMPRESS_TIERS + ["lanes-per8"]
 # chains = the default (decode_chains.hip after the small-block policy); wave-only = no pre-pass; serial = decompress.hip's tag-by-tag kernel;
 # small* = every block through the small-block pre-pass first (decompress_small.hip), leftovers to the list kernel (or one workgroup each: -grid)
 DECODE_LAYOUTS = ["chains", "wave-only", "serial", "small", "small-grid", "small-lanes", "small-team4", "small-team8", "small-team16"]

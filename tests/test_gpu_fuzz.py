@@ -16,6 +16,7 @@ from conftest import read_testdata
 pytestmark = pytest.mark.gpu
 
 import layouts
+from compress_inputs import EDGE_LENGTHS, make_block   # noqa: F401  (the generator lives in compress_inputs.py, importable without the native library)
 
 if torch.cuda.is_available():
     import snappier_amd as S
@@ -25,8 +26,6 @@ ROUNDS = int(os.environ.get("FUZZ_ROUNDS", "2"))
 BLOCKS = int(os.environ.get("FUZZ_BLOCKS", "768"))
 SEED0 = int(os.environ.get("FUZZ_SEED", "0")) * 1000003             # FUZZ_SEED=k: the same tests on other inputs (a long session per k)
 THREADS = min(os.cpu_count() or 1, 64)
-EDGE_LENGTHS = [0, 1, 3, 4, 14, 15, 16, 17, 18, 19, 31, 32, 60, 61, 64, 65, 255, 256, 257, 4095, 4096, 16383, 16384, 16385,
-                32768, 65520, 65521, 65535, 65536]
 
 
 def log_session(**kw):
@@ -37,52 +36,6 @@ def log_session(**kw):
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "fuzz_log.jsonl"), "a") as f:
         f.write(json.dumps(kw) + "\n")
-
-
-def make_block(rng: np.random.Generator, text: np.ndarray) -> np.ndarray:
-    n = int(rng.choice(EDGE_LENGTHS)) if rng.integers(0, 3) == 0 else int(rng.integers(0, 65537))
-    kind = int(rng.integers(0, 7))
-    if kind == 0:                                             # incompressible
-        return rng.integers(0, 256, n, dtype=np.uint8)
-    if kind == 1:                                             # text window with mutations
-        s = int(rng.integers(0, len(text)))
-        b = np.resize(np.roll(text, -s), n).copy()
-        k = int(rng.integers(0, max(1, n // 20) + 1))
-        if n and k:
-            b[rng.integers(0, n, k)] = rng.integers(0, 256, k, dtype=np.uint8)
-        return b
-    if kind == 2:                                             # tiny alphabet: long matches, pattern copies
-        return rng.integers(0, int(rng.integers(1, 4)), n, dtype=np.uint8)
-    if kind == 3:                                             # runs of random length
-        out = np.empty(n, dtype=np.uint8)
-        pos = 0
-        while pos < n:
-            L = int(rng.integers(1, 1 << int(rng.integers(1, 11))))
-            out[pos:pos + L] = rng.integers(0, 256)
-            pos += L
-        return out
-    if kind == 4:                                             # random bytes with repeats copied from random distances
-        out = rng.integers(0, 256, n, dtype=np.uint8)
-        pos = 0
-        while pos < n:
-            pos += int(rng.integers(1, 200))
-            if pos >= n:
-                break
-            dist = int(rng.integers(1, min(pos, 65535) + 1))
-            L = min(int(rng.integers(4, 1 << int(rng.integers(3, 9)))), n - pos)
-            for i in range(0, L, dist):                       # forward copy semantics (overlap allowed)
-                out[pos + i: pos + min(i + dist, L)] = out[pos + i - dist: pos - dist + min(i + dist, L)]
-            pos += L
-        return out
-    if kind == 5:                                             # periodic pattern with a defect now and then
-        P = int(rng.integers(1, 70))
-        b = np.resize(rng.integers(0, 256, P, dtype=np.uint8), n).copy()
-        k = int(rng.integers(0, 6))
-        if n and k:
-            b[rng.integers(0, n, k)] ^= 0xFF
-        return b
-    a, c = make_block(rng, text), make_block(rng, text)       # two halves of different kinds
-    return np.concatenate([a[: len(a) // 2], c[: len(c) // 2]])[:65536]
 
 
 def batch_of(blocks):
