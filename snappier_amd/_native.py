@@ -173,6 +173,11 @@ _EXTENSIONS = {
     "frame_chunked": ("libsnappier_hip_frame_chunked.so", "snappier_hip_frame_chunked.h", {
         "snp_frame_encode_chunked_workspace": (_u64, [_u32, _u32, _u32]),
         "snp_frame_encode_chunked_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch update of seekable framed streams through their index: only the chunks the requests touch are compressed again
+    "frame_update": ("libsnappier_hip_frame_update.so", "snappier_hip_frame_update.h", {
+        "snp_frame_write_indexed_workspace": (_u64, [_u32, _u32, _u32, _u64]),
+        "snp_frame_write_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u64,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -214,6 +219,7 @@ LAYOUT_PATH = _extension_path("layout")
 FRAME_RANGE_PATH = _extension_path("frame_range")
 FRAME_INDEX_PATH = _extension_path("frame_index")
 FRAME_CHUNKED_PATH = _extension_path("frame_chunked")
+FRAME_UPDATE_PATH = _extension_path("frame_update")
 
 
 def buffers_lib() -> C.CDLL:
@@ -251,6 +257,11 @@ def frame_chunked_lib() -> C.CDLL:
     return _extension("frame_chunked")
 
 
+def frame_update_lib() -> C.CDLL:
+    """libsnappier_hip_frame_update.so (include/snappier_hip_frame_update.h)."""
+    return _extension("frame_update")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -277,6 +288,10 @@ def frame_index_declared_symbols() -> list[str]:
 
 def frame_chunked_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_chunked"))
+
+
+def frame_update_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_update"))
 
 
 def status_string(st: int) -> str:

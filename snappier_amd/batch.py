@@ -566,6 +566,81 @@ class BlockCodec:
                                                      max_chunks=min(need[0], 0xFFFFFFFF), edge_cap=need[2])
         return out[:need[-1]], out_off, out_len, status
 
+    def frame_write_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", req_stream: torch.Tensor,
+                            req_off: torch.Tensor, data: torch.Tensor, data_off: torch.Tensor, data_len: torch.Tensor, out: torch.Tensor,
+                            out_off: torch.Tensor, out_cap: torch.Tensor, max_slots: int | None = None, stage_cap: int | None = None,
+                            work: torch.Tensor | None = None, with_bound: bool = False):
+        """Replace decoded bytes of framed streams through their chunk index (snp_frame_write_indexed_batch, libsnappier_hip_frame_update.so):
+        -> (out_len, status, req_status, FrameIndex, result, out_bound | None).
+
+        Request r replaces bytes [req_off[r], req_off[r] + data_len[r]) of what stream req_stream[r] (int32) decodes to by
+        data[data_off[r] .. +data_len[r]); requests are sorted by (req_stream, req_off) and byte-disjoint.  The new stream of b goes to
+        out[out_off[b] .. +out_cap[b]): only the chunks a request touches are compressed again, every other byte is a copy; a stream no request
+        names has out_len 0, a stream with a failing request is not written (include/snappier_hip_frame_update.h).  The returned FrameIndex
+        shares first, start, total and tail with `index` and carries the positions of the new streams (for a stream that was not written:
+        the old ones).  result is the 4-element int64 d_result: [0] = dirty slots needed, [1] = sum of out_len over the written streams, [2] =
+        staging bytes needed, [3] = streams written.  Default max_slots and stage_cap: a first call with both 0 (it plans and writes nothing
+        but copies of streams named by empty requests only), then a synchronising read of its d_result.  A caller that passes max_slots,
+        stage_cap and work enqueues only."""
+        self._bind()
+        nreq, ns = req_stream.numel(), in_len.numel()
+        if req_stream.dtype != torch.int32:
+            raise ValueError("frame_write_indexed: req_stream must be an int32 tensor")
+        UL = N.frame_update_lib()
+        busy = nreq and ns
+        framed, out, data = self._readable(framed, busy), self._readable(out, busy), self._readable(data, busy)
+        out_len = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        status = torch.zeros(ns, dtype=torch.int32, device=self.device)
+        req_status = torch.full((nreq,), N.ERR_BAD_ARG, dtype=torch.int32, device=self.device)     # (no stream at all: no request names one)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        ne = index.nentries
+        new_pos = index.pos[:ne].clone()
+        bound = torch.zeros(ns, dtype=torch.int64, device=self.device) if with_bound else None
+        start, pos = self._readable(index.start, busy), self._readable(index.pos, busy)
+
+        def call(ms: int, sc: int, w: torch.Tensor | None):
+            w = self._work("frame_write_indexed", w, UL.snp_frame_write_indexed_workspace, ns, nreq, ms, sc)
+            st = UL.snp_frame_write_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                                  _p(index.total), _p(index.tail), ne, _p(data), _p(req_stream), _p(req_off), _p(data_len),
+                                                  _p(data_off), nreq, ms, sc, _p(out), _p(out_off), _p(out_cap), _p(out_len), _p(status),
+                                                  _p(req_status), _p(new_pos), _p(bound), _p(w), _p(result))
+            raise_for_status(st, self.ctx.handle)
+
+        if max_slots is None or stage_cap is None:
+            call(0, 0, None)
+            need = result.tolist()
+            max_slots = min(need[0], 0xFFFFFFFF) if max_slots is None else max_slots
+            stage_cap = need[2] if stage_cap is None else stage_cap
+        call(max_slots, stage_cap, work)
+        return out_len, status, req_status, FrameIndex(index.first, index.start, new_pos, index.total, index.tail, result), result, bound
+
+    def frame_update_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", req_stream: torch.Tensor,
+                               req_off: torch.Tensor, data: torch.Tensor, data_off: torch.Tensor, data_len: torch.Tensor, align: int = 1,
+                               max_bytes: int | None = None):
+        """Update framed streams given the framed tensor, its table, its index and the requests:
+        -> (out, out_off, out_len, status, req_status, FrameIndex).
+
+        ONE sizing call (max_slots = stage_cap = 0, every out_cap 0: nothing is written) that also asks for each named stream's size bound,
+        ONE synchronising read of its result and of the arena size (ValueError if that is above max_bytes), an arena in which stream b's slot
+        is its bound rounded up to `align` (0 for a stream that is left alone or refused), then the write.  Streams with out_len 0 are not in
+        the arena: the caller keeps their old bytes, and the returned index holds their old positions."""
+        ns = in_len.numel()
+        zero = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        empty = torch.empty(0, dtype=torch.uint8, device=self.device)
+        _, _, _, _, result, bound = self.frame_write_indexed(framed, in_off, in_len, index, req_stream, req_off, data, data_off, data_len, empty,
+                                                             zero, zero, 0, 0, with_bound=True)
+        slot = (bound + (align - 1)) // align * align
+        ends = torch.cumsum(slot, 0)
+        out_off = ends - slot
+        need = torch.cat([result, ends[-1:] if ns else zero[:0].new_zeros(1)]).tolist()
+        if max_bytes is not None and need[-1] > max_bytes:
+            raise ValueError(f"frame_update_to_memory: the new streams take up to {need[-1]} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need[-1], 1), dtype=torch.uint8, device=self.device)
+        out_len, status, req_status, new_index, _, _ = self.frame_write_indexed(framed, in_off, in_len, index, req_stream, req_off, data, data_off,
+                                                                                data_len, out, out_off, bound, max_slots=min(need[0], 0xFFFFFFFF),
+                                                                                stage_cap=need[2])
+        return out[:need[-1]], out_off, out_len, status, req_status, new_index
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()
