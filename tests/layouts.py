@@ -15,7 +15,10 @@ COMPRESS_LAYOUTS = ["win", "win-np2", "wing", "wind", "lanes", "lanes-exact", "l
 COMPRESS_TIERS = ["lanes-opts71-slots2-per16", "lanes-opts71-slots2-per32", "lanes-opts87-slots2-per32", "lanes-opts215-slots1-per64"]
 COMPRESS_LAYOUTS += COMPRESS_TIERS + ["lanes-per8"]
 # chains = the default (decode_chains.hip after the small-block policy); wave-only = no pre-pass; serial = decompress.hip's tag-by-tag kernel;
-# small* = every block through the small-block pre-pass first (decompress_small.hip), leftovers to the list kernel (or one workgroup each: -grid)
+# small* = every block through the small-block pre-pass first (decompress_small.hip), leftovers to the list kernel -- except small-grid, which
+# runs NO pre-pass: SNP_OPT_DECODE_LEFTOVERS = 1 without a pinned pre-pass layout makes launch_decompress (capi_batch.hip: prepass = redo_list ||
+# !chains || pinned || (!redo_grid && !hint_mostly_large)) skip it, so every block goes one per wavefront (k_decode_chains) and the capacities
+# are sampled for the next batch's hint; the pre-pass with one workgroup per leftover needs !chains, which no option of the product sets
 DECODE_LAYOUTS = ["chains", "wave-only", "serial", "small", "small-grid", "small-lanes", "small-team4", "small-team8", "small-team16"]
 
 
@@ -55,7 +58,7 @@ def set_decode_layout(ctx, decode: str, fenced=None, small_max: int = 65536):
                                              "team8": N.DECODE_SMALL_TEAM8, "team16": N.DECODE_SMALL_TEAM16}[kind])
         ctx.set_option(N.OPT_SMALL_BLOCK_MIN_BATCH, 1)
         ctx.set_option(N.OPT_SMALL_BLOCK_MAX, small_max)
-        ctx.set_option(N.OPT_DECODE_LEFTOVERS, 1 if kind == "grid" else 2)   # always the pre-pass, whatever the previous batch was like
+        ctx.set_option(N.OPT_DECODE_LEFTOVERS, 1 if kind == "grid" else 2)   # 2: always the pre-pass, whatever the previous batch was like (1: never, see above)
     else:
         raise ValueError(decode)
     return ctx

@@ -3,8 +3,6 @@
 canary bytes around every output range and guard words around every array and the workspace; equality with snp_frame_encode_buffers_batch at
 65536; the encoder's index against snp_frame_index_batch over the emitted streams and through snp_frame_read_indexed_batch; out_cap and
 max_chunks failures; a buffer past 4 GiB; graph capture; the empty batch.  Needs an MI355X."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -13,39 +11,15 @@ import frame_buffers_helpers as H
 import frame_chunked_model as K
 import oracle as O
 from conftest import read_testdata
+from seekable_cases import windows
+from seekable_harness import CANARY, KEYS, Encoded, Guarded
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from snappier_amd import batch as SB, _native as N
 
-GUARD = 16                 # guard elements on each side of every guarded array
-CANARY = H.CANARY
 VARIANTS = [O.HASH_CRC32C, O.HASH_MUL]
-KEYS = ("first", "start", "pos", "total", "tail")
-
-
-class Guarded:
-    """An array between guard elements: the call gets the middle, the test checks the rims."""
-
-    def __init__(self, n: int, dtype):
-        self.n = n
-        self.t = torch.empty(n + 2 * GUARD, dtype=dtype, device="cuda")
-        self.t.view(torch.uint8).fill_(CANARY)
-        self.mid = self.t[GUARD:GUARD + n]
-
-    def ptr(self):
-        return C.c_void_p(self.t.data_ptr() + GUARD * self.t.element_size())   # (valid for n == 0 too, where an empty view has no address)
-
-    def read(self):
-        h = self.t.cpu().numpy()
-        rim = np.concatenate([h[:GUARD], h[GUARD + self.n:]])
-        assert (rim.view(np.uint8) == CANARY).all(), "a write outside an array"
-        return h[GUARD:GUARD + self.n].astype(np.int64).tolist()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
 
 
 @pytest.fixture(scope="module")
@@ -53,57 +27,6 @@ def content():
     html = read_testdata("html") * 4
     rnd = np.random.default_rng(3).integers(0, 256, 200000, dtype=np.uint8).tobytes()
     return html, rnd
-
-
-class Encoded:
-    """One call of snp_frame_encode_chunked_batch, made directly with every array guarded and the output arena canary-filled: .got is what the
-    model's encode() returns; the device tensors stay for the calls that read the streams back."""
-
-    def __init__(self, cd, blobs, cb, max_chunks=None, caps=None, with_index=True):
-        nb = len(blobs)
-        CL = N.frame_chunked_lib()
-        cd._bind()
-        self.data, in_off, lens = H.pack(blobs)
-        caps = np.array([K.frame_cap(len(x), cb) for x in blobs] if caps is None else caps, dtype=np.int64)
-        self.out_off, total = H.out_layout(caps)
-        self.out = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda")
-        mc = sum(K.nchunks(len(x), cb) for x in blobs) if max_chunks is None else max_chunks
-        self.mc = mc
-        self.out_len, self.status, self.result = Guarded(nb, torch.int64), Guarded(nb, torch.int32), Guarded(4, torch.int64)
-        self.ix = [Guarded(nb + 1, torch.int64), Guarded(mc, torch.int64), Guarded(mc, torch.int64), Guarded(nb, torch.int64), Guarded(nb, torch.int32)]
-        work = Guarded(CL.snp_frame_encode_chunked_workspace(nb, mc, cb), torch.uint8)
-        self.tabs = [H.dev(in_off), H.dev(lens), H.dev(self.out_off), H.dev(caps)]
-        ixp = [g.ptr() for g in self.ix] if with_index else [None] * 5
-        st = CL.snp_frame_encode_chunked_batch(cd.ctx.handle, _p(self.data), _p(self.tabs[0]), _p(self.tabs[1]), nb, cb, mc, _p(self.out),
-                                               _p(self.tabs[2]), _p(self.tabs[3]), self.out_len.ptr(), self.status.ptr(), *ixp, work.ptr(),
-                                               self.result.ptr())
-        assert st == O.OK
-        torch.cuda.synchronize()
-        work.read()
-        status, out_len = self.status.read(), self.out_len.read()
-        self.h = self.out.cpu().numpy()
-        # nothing outside [out_off, out_off + out_len) of an OK buffer; a buffer that is not OK (out_len 0) has its whole range left untouched
-        assert (H.outside_ranges(self.h, self.out_off, out_len) == CANARY).all(), "a write outside the output ranges"
-        streams = [self.h[o:o + n].tobytes() if s == O.OK else None for s, n, o in zip(status, out_len, self.out_off.tolist())]
-        self.got = {"status": status, "out_len": out_len, "streams": streams, "result": self.result.read(), **{k: [] for k in KEYS}}
-        index = [g.read() for g in self.ix]
-        untouched = int.from_bytes(bytes([CANARY]) * 8, "little", signed=True)
-        if with_index:
-            used = index[0][nb]
-            assert 0 <= used <= mc and all(v == untouched for v in index[1][used:] + index[2][used:]), "a row beyond the index"
-            index[1], index[2] = index[1][:used], index[2][:used]
-            self.got.update(zip(KEYS, index))
-        else:
-            assert all((g.t.view(torch.uint8) == CANARY).all() for g in self.ix), "an index array written without an index"
-
-    def frame_index(self):
-        """The encoder's index as the wrapper's calls take it (the arrays the call wrote, on the device)."""
-        return SB.FrameIndex(*[g.mid for g in self.ix], None)
-
-
-def windows(n: int, cb: int):
-    """(offset, length): on a chunk boundary, one byte either side of it, inside one chunk, across three chunks, at the tail -- and past it."""
-    return [(cb, cb), (cb - 1, 2), (1, max(cb - 2, 1)), (cb // 2, 2 * cb + (cb == 1)), (max(n - cb - 1, 0), cb + 5), (n, 3), (0, 1 << 62)]
 
 
 def check(cd, blobs, cb, variant, read=True, **bounds):

@@ -3,8 +3,6 @@ arrays, every output and both d_results against the model (frame_index_model.py)
 words around every output array, the index arrays and both workspaces, a canary-filled arena; all windows of all streams as the requests of one
 call; equality with the device range call; many requests on one stream; the same index after the streams moved; admission by each bound;
 corruption inside and outside the window; a stale index; the empty calls, the gather round trip and graph capture.  Needs an MI355X."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -13,6 +11,7 @@ import frame_buffers_helpers as H
 import frame_index_model as X
 import frame_range_model as R
 import oracle as O
+from seekable_harness import CANARY, Guarded, dev_i32, dev_u64, index_call, read_call
 
 pytestmark = pytest.mark.gpu
 
@@ -20,99 +19,11 @@ if torch.cuda.is_available():
     from snappier_amd import batch as SB, _native as N
 
 B = 65536
-GUARD = 16                 # guard elements on each side of every guarded array
-CANARY = 0x5A
 BIG = 1 << 62
-
-
-def dev_u64(a):
-    """u64 values as the bits of an int64 tensor."""
-    return torch.from_numpy(np.array([(int(x) & R.U64) - (1 << 64) if (int(x) & R.U64) >= 1 << 63 else int(x) & R.U64 for x in a], dtype=np.int64)).cuda()
-
-
-def dev_i32(a):
-    return torch.from_numpy(np.array([int(x) for x in a], dtype=np.int32)).cuda()
-
-
-class Guarded:
-    """An array between guard elements: the call gets the middle, the test checks the rims."""
-
-    def __init__(self, n: int, dtype):
-        self.n = n
-        self.t = torch.empty(n + 2 * GUARD, dtype=dtype, device="cuda")
-        self.t.view(torch.uint8).fill_(CANARY)
-        self.mid = self.t[GUARD:GUARD + n]
-
-    def ptr(self):
-        return C.c_void_p(self.mid.data_ptr())                          # (valid for n == 0 too: nothing is written there)
-
-    def read(self):
-        h = self.t.cpu().numpy()
-        rim = np.concatenate([h[:GUARD], h[GUARD + self.n:]])
-        assert (rim.view(np.uint8) == CANARY).all(), "a write outside an array"
-        return h[GUARD:GUARD + self.n].astype(np.int64).tolist()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def codec():
     return SB.BlockCodec(0, O.HASH_CRC32C)
-
-
-def index_call(cd, streams, max_spans=None, max_entries=None, lead=1, gap=3):
-    """snp_frame_index_batch called directly, every array guarded: -> the index as the model states it (dict of lists, with result)."""
-    ns = len(streams)
-    IL = N.frame_index_lib()
-    cd._bind()
-    want = X.build_index(streams)
-    max_spans = want["result"][2] if max_spans is None else max_spans
-    max_entries = want["result"][0] if max_entries is None else max_entries
-    framed, in_off, in_len = H.pack(streams, lead, gap) if ns else (torch.zeros(16, dtype=torch.uint8, device="cuda"), [], [])
-    first, total, tail = Guarded(ns + 1, torch.int64), Guarded(ns, torch.int64), Guarded(ns, torch.int32)
-    start, pos, result = Guarded(max_entries, torch.int64), Guarded(max_entries, torch.int64), Guarded(4, torch.int64)
-    work = Guarded(IL.snp_frame_index_workspace(ns, max_spans), torch.uint8)
-    tabs = [dev_u64(in_off), dev_u64(in_len)]
-    st = IL.snp_frame_index_batch(cd.ctx.handle, _p(framed), _p(tabs[0]), _p(tabs[1]), ns, max_spans, max_entries, first.ptr(), start.ptr(), pos.ptr(),
-                                  total.ptr(), tail.ptr(), work.ptr(), result.ptr())
-    assert st == O.OK
-    torch.cuda.synchronize()
-    work.read()
-    ix = {"first": first.read(), "start": start.read(), "pos": pos.read(), "total": total.read(), "tail": tail.read(), "result": result.read()}
-    used = ix["first"][ns] if ns else 0
-    assert 0 <= used <= max_entries
-    assert all(v == int.from_bytes(bytes([CANARY]) * 8, "little", signed=True) for v in ix["start"][used:] + ix["pos"][used:]), "a row beyond the index"
-    ix["start"], ix["pos"] = ix["start"][:used], ix["pos"][:used]
-    return ix
-
-
-def read_call(cd, streams, ix, requests, caps, mc, ec, lead=1, gap=3, nentries=None):
-    """snp_frame_read_indexed_batch called directly, every output guarded, the arena canary-filled:
-    -> (status, out_len, bytes per request (None unless OK), d_result)."""
-    ns, nreq = len(streams), len(requests)
-    IL = N.frame_index_lib()
-    cd._bind()
-    framed, in_off, in_len = H.pack(streams, lead, gap) if ns else (torch.zeros(16, dtype=torch.uint8, device="cuda"), [], [])
-    out_off, total = H.out_layout(caps)
-    out = torch.full((max(total, 1),), CANARY, dtype=torch.uint8, device="cuda")
-    out_len, status, result = Guarded(nreq, torch.int64), Guarded(nreq, torch.int32), Guarded(4, torch.int64)
-    work = Guarded(IL.snp_frame_read_indexed_workspace(nreq, mc, ec), torch.uint8)
-    ne = min(len(ix["start"]), len(ix["pos"])) if nentries is None else nentries
-    tabs = [dev_u64(x) for x in (in_off, in_len, ix["first"], ix["start"] or [0], ix["pos"] or [0], ix["total"])] + [dev_i32(ix["tail"])] + \
-        [dev_i32([b - (1 << 32) if b >= 1 << 31 else b for b, _, _ in requests])] + \
-        [dev_u64(x) for x in ([r[1] for r in requests], [r[2] for r in requests], out_off, caps)]   # (named: they outlive the call)
-    st = IL.snp_frame_read_indexed_batch(cd.ctx.handle, _p(framed), _p(tabs[0]), _p(tabs[1]), ns, *[_p(t) for t in tabs[2:7]], ne,
-                                         _p(tabs[7]), _p(tabs[8]), _p(tabs[9]), nreq, mc, ec, _p(out), _p(tabs[10]), _p(tabs[11]),
-                                         out_len.ptr(), status.ptr(), work.ptr(), result.ptr())
-    assert st == O.OK
-    torch.cuda.synchronize()
-    work.read()
-    st, ol, res, h = status.read(), out_len.read(), result.read(), out.cpu().numpy()
-    # nothing outside [out_off, out_off + out_len) of an OK request, nor outside [out_off, out_off + out_cap) of any other
-    assert (H.outside_ranges(h, out_off, [n if s == O.OK else c for s, n, c in zip(st, ol, caps)]) == CANARY).all(), "a write outside the output ranges"
-    data = [h[o:o + n].tobytes() if s == O.OK else None for s, n, o in zip(st, ol, out_off.tolist())]
-    return st, ol, data, res
 
 
 def check(cd, streams, ix, requests, caps, mc=None, ec=None, **where):

@@ -3,8 +3,6 @@
 smallest shapes that can go wrong (1-5 chunks, tiny foreign chunks, a chunk above 65536 bytes as an edge, a window in the second span); equality
 with frame_decode_buffers sliced on the host; admission by each bound; the capacity; corruption inside and outside the window; the read_to_memory
 round trips; graph capture; an empty batch.  Needs an MI355X."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -14,6 +12,7 @@ import frame_buffers_helpers as H
 import frame_buffers_model as M
 import frame_range_model as R
 import oracle as O
+from seekable_harness import CANARY, Guarded, dev_u64, range_call
 
 pytestmark = pytest.mark.gpu
 
@@ -21,68 +20,6 @@ if torch.cuda.is_available():
     from snappier_amd import batch as SB, _native as N
 
 B = 65536
-GUARD = 16                 # guard elements on each side of every output array
-CANARY = 0x5A
-
-
-def dev_u64(a):
-    """u64 values as the bits of an int64 tensor."""
-    return torch.from_numpy(np.array([int(x) - (1 << 64) if int(x) >= 1 << 63 else int(x) for x in a], dtype=np.int64)).cuda()
-
-
-class Guarded:
-    """An output array between guard elements: the call gets the middle, the test checks the rims."""
-
-    def __init__(self, n: int, dtype):
-        self.n = n
-        self.t = torch.empty(n + 2 * GUARD, dtype=dtype, device="cuda")
-        self.t.view(torch.uint8).fill_(CANARY)
-        self.mid = self.t[GUARD:GUARD + n]
-
-    def ptr(self):
-        return C.c_void_p(self.mid.data_ptr())                          # (valid for n == 0 too: nothing is written there)
-
-    def read(self):
-        h = self.t.cpu().numpy()
-        rim = np.concatenate([h[:GUARD], h[GUARD + self.n:]])
-        assert (rim.view(np.uint8) == CANARY).all(), "a write outside an output array"
-        return h[GUARD:GUARD + self.n].astype(np.int64).tolist()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def pack_table(streams):
-    """Every distinct stream once (the call only reads `in`: input ranges may overlap): -> (device tensor, in_off, in_len) per entry."""
-    uniq = list(dict.fromkeys(streams))
-    framed, off, _ = H.pack(uniq)
-    where = {s: int(o) for s, o in zip(uniq, off)}
-    return framed, [where[s] for s in streams], [len(s) for s in streams]
-
-
-def range_call(cd, streams, ranges, caps, mc, sp, ec):
-    """snp_frame_decode_range_batch called directly, every output guarded, the arena canary-filled:
-    -> (status, out_len, bytes per stream (None unless OK), d_result)."""
-    ns = len(streams)
-    RL = N.frame_range_lib()
-    cd._bind()
-    framed, in_off, in_len = pack_table(streams) if ns else (torch.zeros(16, dtype=torch.uint8, device="cuda"), [], [])
-    out_off, total = H.out_layout(caps)
-    out = torch.full((max(total, 1),), CANARY, dtype=torch.uint8, device="cuda")
-    out_len, status, result = Guarded(ns, torch.int64), Guarded(ns, torch.int32), Guarded(6, torch.int64)
-    work = Guarded(RL.snp_frame_decode_range_workspace(ns, mc, sp, ec), torch.uint8)
-    tables = [dev_u64(x) for x in (in_off, in_len, [r[0] for r in ranges], [r[1] for r in ranges], out_off, caps)]   # (named: they outlive the call)
-    st = RL.snp_frame_decode_range_batch(cd.ctx.handle, _p(framed), _p(tables[0]), _p(tables[1]), ns, _p(tables[2]), _p(tables[3]), mc, sp, ec,
-                                         _p(out), _p(tables[4]), _p(tables[5]), out_len.ptr(), status.ptr(), work.ptr(), result.ptr())
-    assert st == O.OK
-    torch.cuda.synchronize()
-    work.read()
-    st, ol, res, h = status.read(), out_len.read(), result.read(), out.cpu().numpy()
-    # nothing outside [out_off, out_off + out_len) of an OK stream, nor outside [out_off, out_off + out_cap) of any other
-    assert (H.outside_ranges(h, out_off, [n if s == O.OK else c for s, n, c in zip(st, ol, caps)]) == CANARY).all(), "a write outside the output ranges"
-    data = [h[o:o + n].tobytes() if s == O.OK else None for s, n, o in zip(st, ol, out_off.tolist())]
-    return st, ol, data, res
 
 
 def check(cd, streams, ranges, caps, mc=None, sp=None, ec=None):

@@ -4,8 +4,6 @@ around every array and the workspace; whole-arena equality with snp_frame_encode
 snp_frame_index_batch and through snp_frame_read_indexed_batch; foreign streams; mixed batches; admission; corruption in an edge and in a
 covered chunk; every request error; stale and unsound indexes; the seams of the emit's workgroups; a stream past 4 GiB; graph capture; empty
 calls.  Needs an MI355X."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -18,109 +16,14 @@ import frame_range_model as R
 import frame_update_model as U
 import oracle as O
 from conftest import read_testdata
+from seekable_harness import CANARY, Guarded, Updated, index_tensors
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from snappier_amd import batch as SB, _native as N
 
-GUARD = 16
-CANARY = H.CANARY
 VARIANTS = [O.HASH_CRC32C, O.HASH_MUL]
-UNTOUCHED = int.from_bytes(bytes([CANARY]) * 8, "little", signed=True)
-
-
-def s64(v: int) -> int:
-    v &= U.U64
-    return v - (1 << 64) if v >> 63 else v
-
-
-def s32(v: int) -> int:
-    v &= 0xFFFFFFFF
-    return v - (1 << 32) if v >> 31 else v
-
-
-def words(vals):
-    return H.dev([s64(int(v)) for v in vals])
-
-
-class Guarded:
-    """An array between guard elements: the call gets the middle, the test checks the rims."""
-
-    def __init__(self, n: int, dtype):
-        self.n = n
-        self.t = torch.empty(n + 2 * GUARD, dtype=dtype, device="cuda")
-        self.t.view(torch.uint8).fill_(CANARY)
-        self.mid = self.t[GUARD:GUARD + n]
-
-    def ptr(self):
-        return C.c_void_p(self.t.data_ptr() + GUARD * self.t.element_size())
-
-    def read(self):
-        h = self.t.cpu().numpy()
-        rim = np.concatenate([h[:GUARD], h[GUARD + self.n:]])
-        assert (rim.view(np.uint8) == CANARY).all(), "a write outside an array"
-        return h[GUARD:GUARD + self.n].astype(np.int64).tolist()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t.numel() else C.c_void_p(None)
-
-
-def index_tensors(ix, ns):
-    """The five arrays of a model index (any lists at all) on the device, and nentries."""
-    ne = min(len(ix["start"]), len(ix["pos"]))
-    tail = torch.tensor([s32(v) for v in ix["tail"][:ns]], dtype=torch.int32, device="cuda")
-    return [words(ix["first"][:ns + 1]), words(ix["start"][:ne] or [0]), words(ix["pos"][:ne] or [0]), words(ix["total"][:ns]), tail], ne
-
-
-class Updated:
-    """One call of snp_frame_write_indexed_batch, made directly with every output array guarded and the arena canary-filled; .got has the keys of
-    the model's write_plan.  caps None: the model's size bound (the stream's own length where that is 0).  Bounds None: what the model needs."""
-
-    def __init__(self, cd, streams, ix, reqs, srcs, caps=None, max_slots=None, stage_cap=None, variant=O.HASH_CRC32C):
-        ns, nreq = len(streams), len(reqs)
-        UL = N.frame_update_lib()
-        cd._bind()
-        free = U.write_plan(streams, ix, reqs, srcs, variant=variant)
-        self.caps = caps = [bd or len(s) for bd, s in zip(free["out_bound"], streams)] if caps is None else caps
-        self.ms = ms = free["result"][0] if max_slots is None else max_slots
-        self.sc = sc = free["result"][2] if stage_cap is None else stage_cap
-        self.want = U.write_plan(streams, ix, reqs, srcs, caps, ms, sc, variant)
-        self.data, in_off, lens = H.pack(streams)
-        self.src, src_off, _ = H.pack(srcs, lead=5, gap=2)
-        self.out_off, total = H.out_layout(np.array(caps, dtype=np.int64))
-        self.out = torch.full((total,), CANARY, dtype=torch.uint8, device="cuda")
-        self.ix, ne = index_tensors(ix, ns)
-        self.out_len, self.status, self.req_status = Guarded(ns, torch.int64), Guarded(ns, torch.int32), Guarded(nreq, torch.int32)
-        self.new_pos, self.bound, self.result = Guarded(ne, torch.int64), Guarded(ns, torch.int64), Guarded(4, torch.int64)
-        work = Guarded(UL.snp_frame_write_indexed_workspace(ns, nreq, ms, sc), torch.uint8)
-        self.tabs = [H.dev(in_off), H.dev(lens), H.dev(self.out_off), H.dev(caps), H.dev(src_off),
-                     torch.tensor([s32(q[0]) for q in reqs] or [0], dtype=torch.int32, device="cuda"), words([q[1] for q in reqs] or [0]),
-                     words([q[2] for q in reqs] or [0])]
-        st = UL.snp_frame_write_indexed_batch(cd.ctx.handle, _p(self.data), _p(self.tabs[0]), _p(self.tabs[1]), ns, *[_p(t) for t in self.ix], ne,
-                                              _p(self.src), _p(self.tabs[5]), _p(self.tabs[6]), _p(self.tabs[7]), _p(self.tabs[4]), nreq, ms, sc,
-                                              _p(self.out), _p(self.tabs[2]), _p(self.tabs[3]), self.out_len.ptr(), self.status.ptr(),
-                                              self.req_status.ptr(), self.new_pos.ptr(), self.bound.ptr(), work.ptr(), self.result.ptr())
-        assert st == O.OK
-        torch.cuda.synchronize()
-        work.read()
-        status, out_len = self.status.read(), self.out_len.read()
-        self.h = self.out.cpu().numpy()
-        # nothing outside [out_off, out_off + out_len) of a written stream; any other stream (out_len 0) has its whole range left untouched
-        assert (H.outside_ranges(self.h, self.out_off, out_len) == CANARY).all(), "a write outside the output ranges"
-        new = [self.h[o:o + n].tobytes() if s == O.OK and n else None for s, n, o in zip(status, out_len, self.out_off.tolist())]
-        self.got = dict(status=status, out_len=out_len, streams=new, req_status=self.req_status.read(), new_pos=self.new_pos.read(),
-                        out_bound=self.bound.read(), result=self.result.read())
-
-    def check(self):
-        w = self.want
-        for key in ("status", "out_len", "req_status", "result", "out_bound"):
-            assert self.got[key] == w[key], key
-        assert self.got["new_pos"] == [s64(v) for v in w["new_pos"]]
-        for b, (g, x) in enumerate(zip(self.got["streams"], w["streams"])):
-            assert g == (x or None), b                                  # (a written stream of no bytes reads as None here)
-        return self
 
 
 def batch_of(blobs, cb, variant):
