@@ -257,7 +257,9 @@ snp_status snp_decompress_batch(snp_ctx* ctx, const uint8_t* in, const uint64_t*
                                 uint32_t* out_len, int32_t* status);
 
 /* CRC-32C (optionally masked) of nblocks independent byte ranges; wave-parallel (each lane folds its dwords with a GF(2)-linear
- * shift map; which form of the map runs is SNP_OPT_CRC_KERNEL: by default sliced 11 + 11 + 10 bits out of three LDS tables, crc32c.hip). */
+ * shift map; which form of the map runs is SNP_OPT_CRC_KERNEL: by default sliced 11 + 11 + 10 bits out of three LDS tables, crc32c.hip).
+ * Under option 0 a call with nblocks < 16 384 runs the four 8-bit tables instead (one range per wavefront; the three-table kernel takes four
+ * consecutive ranges per wavefront); the result is the same.  in_len[b] may be any uint32_t: one wavefront reads a range, 64 KiB or 4 GiB - 1. */
 snp_status snp_crc32c_batch(snp_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
                             uint32_t nblocks, int masked, uint32_t* out_crc);
 

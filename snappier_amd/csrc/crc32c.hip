@@ -145,21 +145,25 @@ __global__ __launch_bounds__(SNP_WAVE * (MODE == 2 ? kWaves11 : kCrcWaves)) void
         crc = s ^ 0xffffffffu;
     } else {
         const u32 padb = (1024u - (n & 1023u)) & 1023u;                 // virtual leading zero bytes
-        const u32 rows = (n + padb) >> 10;
+        const u32 rows = static_cast<u32>((static_cast<u64>(n) + padb) >> 10);   // (n + padb reaches 2^32: n goes up to 2^32 - 1)
         u32 acc[4] = {0, 0, 0, 0};
-        // this lane's 16 bytes of row i start at src + i*1024 + lane*16 - padb
+        // this lane's 16 bytes of row i start rel = i*1024 + lane*16 bytes past pad0 = src - padb, the start of the padded message.  rows <= 2^22, so
+        // rel fits u32 for every n that u32 holds.  Counted from src the offset is rel - padb: negative in the pad and up to 2^32 - 16, which no 32-bit
+        // type holds (as i32 it sent every row from byte 2^31 on into the pad branch) -- hence pad0 and the unsigned rel: nothing 64-bit in the row loop
+        const u8* pad0 = src - padb;                                    // (up to 1023 bytes before the range: nothing below src is read)
         auto load_row = [&](u32 i, u32 (&w)[4]) {
-            const i32 rbyte = static_cast<i32>(i * 1024u + lane * 16u) - static_cast<i32>(padb);
-            if (rbyte >= 4) {
+            const u32 rel = i * 1024u + lane * 16u;
+            const i32 rbyte = static_cast<i32>(rel - padb);             // the offset from src: exact in rows 0 and 1, where the branch below uses it
+            if (rel >= padb + 4u) {                                     // all 16 bytes inside the range and past the four inverted ones
 #if SNP_CRC_NT
                 typedef u32 u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
-                const u32x4_u q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_u*>(src + rbyte));   // read once, never again: do not keep it in L2
+                const u32x4_u q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_u*>(pad0 + rel));   // read once, never again: do not keep it in L2
                 w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
 #else
-                const snp_u128_unaligned q = *reinterpret_cast<const snp_u128_unaligned*>(src + rbyte);
+                const snp_u128_unaligned q = *reinterpret_cast<const snp_u128_unaligned*>(pad0 + rel);
                 w[0] = q.v[0]; w[1] = q.v[1]; w[2] = q.v[2]; w[3] = q.v[3];
 #endif
-            } else {                                                    // first row only: leading pad and the init xor
+            } else {                                                    // rows 0 and 1 only: leading pad and the init xor (row 0 may hold fewer than four bytes)
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
                     w[d] = 0;

@@ -301,10 +301,12 @@ def test_context_options_pin_layouts_without_changing_results():
 
 
 def test_crc32c_table_free_kernel_equals_the_table_kernel_and_the_oracle():
-    """SNP_OPT_CRC_KERNEL = 1 (the kernel BASELINE.json's north star names: no table, the GF(2) shift map bit by bit), 0 (the default: three
-    LDS tables of 11 + 11 + 10 bits, four byte ranges per wavefront -- so the ragged list also ends inside a wavefront's group of four) and 2 (round 3's
-    four 8-bit tables) against the oracle (Crc32CAlgorithm.cs:41-158): ragged lengths 0 .. 70 000, masked and unmasked, and through the
-    framing format (snp_frame_encode computes every chunk's CRC with the selected kernel, snp_frame_decode verifies with it)."""
+    """SNP_OPT_CRC_KERNEL = 1 (the kernel BASELINE.json's north star names: no table, the GF(2) shift map bit by bit), 0 (the default) and 2
+    (round 3's four 8-bit tables) against the oracle (Crc32CAlgorithm.cs:41-158): ragged lengths 0 .. 70 000, masked and unmasked, and through
+    the framing format (snp_frame_encode computes every chunk's CRC with the selected kernel, snp_frame_decode verifies with it).  At 218
+    ranges option 0 runs the four 8-bit tables as well (k_crc32c<0>: snp_launch_crc32c takes the three LDS tables of 11 + 11 + 10 bits, four
+    byte ranges per wavefront, from 16 384 ranges on), so this test runs k_crc32c<1> and k_crc32c<0>; the three-table kernel on ragged lists
+    that end inside a wavefront's group of four is test_gpu_crc32c_kernels.py."""
     N = S._native
     cd = SB.BlockCodec(0, O.HASH_CRC32C)
     rng = np.random.default_rng(11)
