@@ -178,6 +178,11 @@ _EXTENSIONS = {
         "snp_frame_write_indexed_workspace": (_u64, [_u32, _u32, _u32, _u64]),
         "snp_frame_write_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u64,
                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch append to seekable framed streams, in place: the tail chunk reopened, fresh chunks behind it, the new index
+    "frame_append": ("libsnappier_hip_frame_append.so", "snappier_hip_frame_append.h", {
+        "snp_frame_append_indexed_workspace": (_u64, [_u32, _u32, _u32, _u32]),
+        "snp_frame_append_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u32, _u32,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -220,6 +225,7 @@ FRAME_RANGE_PATH = _extension_path("frame_range")
 FRAME_INDEX_PATH = _extension_path("frame_index")
 FRAME_CHUNKED_PATH = _extension_path("frame_chunked")
 FRAME_UPDATE_PATH = _extension_path("frame_update")
+FRAME_APPEND_PATH = _extension_path("frame_append")
 
 
 def buffers_lib() -> C.CDLL:
@@ -262,6 +268,11 @@ def frame_update_lib() -> C.CDLL:
     return _extension("frame_update")
 
 
+def frame_append_lib() -> C.CDLL:
+    """libsnappier_hip_frame_append.so (include/snappier_hip_frame_append.h)."""
+    return _extension("frame_append")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -292,6 +303,10 @@ def frame_chunked_declared_symbols() -> list[str]:
 
 def frame_update_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_update"))
+
+
+def frame_append_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_append"))
 
 
 def status_string(st: int) -> str:

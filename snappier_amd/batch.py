@@ -641,6 +641,63 @@ class BlockCodec:
                                                                                 stage_cap=need[2])
         return out[:need[-1]], out_off, out_len, status, req_status, new_index
 
+    def frame_append_indexed(self, buf: torch.Tensor, buf_off: torch.Tensor, buf_len: torch.Tensor, buf_cap: torch.Tensor, index: "FrameIndex",
+                             data: torch.Tensor, data_off: torch.Tensor, data_len: torch.Tensor, chunk_bytes: int, max_tails: int, max_slots: int,
+                             work: torch.Tensor | None = None, with_bound: bool = False):
+        """Append bytes to framed streams in place, through their chunk index (snp_frame_append_indexed_batch, libsnappier_hip_frame_append.so):
+        -> (new_len, status, FrameIndex, result, out_bound | None).  The direct call: it enqueues only (it allocates its outputs, and the
+        workspace when `work` is None).
+
+        Stream b is buf[buf_off[b] .. +buf_len[b]) inside a region of buf_cap[b] bytes that it may grow into (int64 tensors, read as unsigned;
+        the regions disjoint); data[data_off[b] .. +data_len[b]) is appended to what it decodes to, in chunks of chunk_bytes.  A short tail
+        chunk that is physically last is reopened and encoded again where it was, the rest follows in fresh chunks; nothing before that is
+        written, and a stream is appended to whole or not at all (new_len[b] = buf_len[b] then: include/snappier_hip_frame_append.h).  The
+        returned FrameIndex is the batch's index after the call (start / pos hold index.nentries + max_slots rows) and goes straight into
+        frame_read_indexed, frame_write_indexed and the next append, with (buf, buf_off, new_len) as the framed streams.  result is the
+        4-element int64 d_result: [0] = fresh chunk slots needed, [1] = bytes the written streams grew by, [2] = reopened tails needed, [3] =
+        streams written; max_tails = max_slots = 0 is the sizing call."""
+        if not 1 <= chunk_bytes <= N.BLOCK_SIZE:
+            raise ValueError(f"frame_append_indexed: chunk_bytes = {chunk_bytes}, must be 1 .. {N.BLOCK_SIZE}")
+        self._bind()
+        ns = buf_len.numel()
+        AL = N.frame_append_lib()
+        buf, data = self._readable(buf, ns), self._readable(data, ns)
+        ne = index.nentries
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+        new_len = torch.empty(ns, dtype=torch.int64, device=self.device)
+        status = torch.empty(ns, dtype=torch.int32, device=self.device)
+        first = torch.zeros(ns + 1, dtype=torch.int64, device=self.device)
+        rows = ne + max_slots
+        new_start = torch.empty(max(rows, 1), dtype=torch.int64, device=self.device)
+        new_pos = torch.empty(max(rows, 1), dtype=torch.int64, device=self.device)
+        total = torch.empty(ns, dtype=torch.int64, device=self.device)
+        tail = torch.empty(ns, dtype=torch.int32, device=self.device)
+        bound = torch.zeros(ns, dtype=torch.int64, device=self.device) if with_bound else None
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        w = self._work("frame_append_indexed", work, AL.snp_frame_append_indexed_workspace, ns, max_tails, max_slots, chunk_bytes)
+        st = AL.snp_frame_append_indexed_batch(self.ctx.handle, _p(buf), _p(buf_off), _p(buf_len), _p(buf_cap), ns, _p(index.first), _p(start), _p(pos),
+                                               _p(index.total), _p(index.tail), ne, _p(data), _p(data_off), _p(data_len), chunk_bytes, max_tails,
+                                               max_slots, _p(new_len), _p(status), _p(first), _p(new_start), _p(new_pos), _p(total), _p(tail),
+                                               _p(bound), _p(w), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return new_len, status, FrameIndex(first, new_start[:rows], new_pos[:rows], total, tail, result), result, bound
+
+    def frame_append_to_memory(self, buf: torch.Tensor, buf_off: torch.Tensor, buf_len: torch.Tensor, buf_cap: torch.Tensor, index: "FrameIndex",
+                               data: torch.Tensor, data_off: torch.Tensor, data_len: torch.Tensor, chunk_bytes: int = N.BLOCK_SIZE):
+        """Append to framed streams given the arena they are kept in, its table, its index and the bytes: -> (new_len, status, FrameIndex).
+
+        ONE sizing call (max_tails = max_slots = 0: nothing is written) with ONE synchronising read of its result, then the workspace, the new
+        index (index.nentries + fresh slots rows: those of a stream that is not written stay unused at the end) and the append.  A stream whose
+        region cannot hold it has status SNP_ERR_OUTPUT_TOO_SMALL and is left as it was: the caller moves it to a larger region and appends
+        again."""
+        _, _, _, result, _ = self.frame_append_indexed(buf, buf_off, buf_len, buf_cap, index, data, data_off, data_len, chunk_bytes, 0, 0)
+        need = result.tolist()
+        if need[0] > 0xFFFFFFFF or need[2] > 0xFFFFFFFF:
+            raise ValueError(f"frame_append_to_memory: {need[0]} chunk slots and {need[2]} tails, one call takes 2^32 - 1 of each")
+        new_len, status, new_index, _, _ = self.frame_append_indexed(buf, buf_off, buf_len, buf_cap, index, data, data_off, data_len, chunk_bytes,
+                                                                     need[2], need[0])
+        return new_len, status, new_index
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()

@@ -22,13 +22,6 @@
 
 namespace {
 
-__constant__ u8 k_fc_stream_id[SNP_STREAM_HEADER_LEN] = {0xff, 0x06, 0x00, 0x00, 0x73, 0x4e, 0x61, 0x50, 0x70, 0x59};   // SnappyStreamCompressor.cs:18-21
-
-__device__ __forceinline__ u32 payload_of(u32 comp, u32 raw, bool* shrink)
-{
-    *shrink = comp < raw;                                               // CompressBlock  SnappyStreamCompressor.cs:212
-    return *shrink ? comp : raw;
-}
 // scan sources: the pieces of a buffer, one framed chunk's size (0 for an empty slot), the rows of a buffer (those of an OK one)
 struct ScanChunks {
     const u64* __restrict__ len;
@@ -108,26 +101,6 @@ __global__ __launch_bounds__(256) void k_fc_streams(u32 nb, const u64* __restric
     const bool ok = status[b] == SNP_OK;
     idx_total[b] = ok ? in_len[b] : 0;
     idx_tail[b] = ok ? SNP_OK : SNP_ERR_OUTPUT_TOO_SMALL;
-}
-
-// len bytes by a team of T threads (t = the thread's place in it), src and dst apart.  From 64 bytes on the destination is brought to a 16-byte
-// boundary by byte stores first -- a chunk lands wherever the scan puts it -- and the body leaves as aligned 16-byte stores; shorter pieces
-// are not worth the head.  All threads of the team must call it.
-__device__ __forceinline__ void team_copy(u8* dst, const u8* src, u32 len, u32 t, u32 T)
-{
-    if (len < 64) {
-        if (t < len) dst[t] = src[t];                                   // (T >= 64)
-        return;
-    }
-    const u32 head = static_cast<u32>(16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u;
-    if (t < head) dst[t] = src[t];
-    const u32 body = (len - head) & ~15u;
-    for (u32 k = t * 16; k < body; k += T * 16) {
-        const snp_u128_unaligned w = *reinterpret_cast<const snp_u128_unaligned*>(src + head + k);
-        *reinterpret_cast<uint4*>(dst + head + k) = make_uint4(w.v[0], w.v[1], w.v[2], w.v[3]);
-    }
-    const u32 done = head + body;
-    if (t < len - done) dst[done + t] = src[done + t];                  // (< 16 bytes)
 }
 
 // [type:1][len:3 LE = payload + 4][masked crc:4 LE][payload]  (:233-261) of every slot of the workgroup, each at its buffer's place: k_fe_emit over

@@ -3,6 +3,8 @@
 // slot's compressed bytes are staged, how many slots one emit workgroup takes, and the index row of a chunk once the scan over the OK buffers'
 // chunk counts exists.  __host__ __device__ throughout, so that the same code runs on the CPU under sanitizers
 // (tests/abi/frame_chunked_plan_check.hip) on buffers past 4 GiB, where k * chunk_bytes does not fit 32 bits.  DESIGN.md 4.15.
+// At the end, device only: what the emit kernel of this call shares with that of the append (frame_append.hip) -- the stream identifier, the
+// CompressBlock rule for a chunk's payload, and team_copy.
 //
 // first[0 .. nb] is the exclusive scan of fc_chunks(in_len[b], cb) (first[nb] = the slots the batch needs); ok_first[0 .. nb] the same scan over
 // the buffers whose status is SNP_OK only, made after the size verdict: an out_cap failure can hit a buffer in the middle of the batch, so the
@@ -61,5 +63,34 @@ __host__ __device__ __forceinline__ u64 fc_stage_off(u32 c, u64 stride) { return
 // the index row of chunk k of an OK buffer whose rows start at ok_first_b (include/snappier_hip_frame_index.h: the decoded bytes before the chunk)
 struct FcRow { u64 row, start; };
 __host__ __device__ __forceinline__ FcRow fc_row(u64 ok_first_b, u64 k, u32 cb) { return FcRow{ok_first_b + k, k * cb}; }
+
+// ---- what the emit kernels of the chunked encode and of the append (frame_append.hip) share -------------------------------------------------------
+__constant__ u8 k_fc_stream_id[SNP_STREAM_HEADER_LEN] = {0xff, 0x06, 0x00, 0x00, 0x73, 0x4e, 0x61, 0x50, 0x70, 0x59};   // SnappyStreamCompressor.cs:18-21
+
+__device__ __forceinline__ u32 payload_of(u32 comp, u32 raw, bool* shrink)
+{
+    *shrink = comp < raw;                                               // CompressBlock  SnappyStreamCompressor.cs:212
+    return *shrink ? comp : raw;
+}
+
+// len bytes by a team of T threads (t = the thread's place in it), src and dst apart.  From 64 bytes on the destination is brought to a 16-byte
+// boundary by byte stores first -- a chunk lands wherever the scan puts it -- and the body leaves as aligned 16-byte stores; shorter pieces
+// are not worth the head.  All threads of the team must call it.
+__device__ __forceinline__ void team_copy(u8* dst, const u8* src, u32 len, u32 t, u32 T)
+{
+    if (len < 64) {
+        if (t < len) dst[t] = src[t];                                   // (T >= 64)
+        return;
+    }
+    const u32 head = static_cast<u32>(16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u;
+    if (t < head) dst[t] = src[t];
+    const u32 body = (len - head) & ~15u;
+    for (u32 k = t * 16; k < body; k += T * 16) {
+        const snp_u128_unaligned w = *reinterpret_cast<const snp_u128_unaligned*>(src + head + k);
+        *reinterpret_cast<uint4*>(dst + head + k) = make_uint4(w.v[0], w.v[1], w.v[2], w.v[3]);
+    }
+    const u32 done = head + body;
+    if (t < len - done) dst[done + t] = src[done + t];                  // (< 16 bytes)
+}
 
 }  // namespace
