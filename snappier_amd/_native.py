@@ -183,6 +183,11 @@ _EXTENSIONS = {
         "snp_frame_append_indexed_workspace": (_u64, [_u32, _u32, _u32, _u32]),
         "snp_frame_append_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u32, _u32,
                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch splice of seekable framed streams: one insert / delete / truncate per stream, the chunks around the hole compressed again, the new index
+    "frame_splice": ("libsnappier_hip_frame_splice.so", "snappier_hip_frame_splice.h", {
+        "snp_frame_splice_indexed_workspace": (_u64, [_u32, _u32, _u64, _u32]),
+        "snp_frame_splice_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u64,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -226,6 +231,7 @@ FRAME_INDEX_PATH = _extension_path("frame_index")
 FRAME_CHUNKED_PATH = _extension_path("frame_chunked")
 FRAME_UPDATE_PATH = _extension_path("frame_update")
 FRAME_APPEND_PATH = _extension_path("frame_append")
+FRAME_SPLICE_PATH = _extension_path("frame_splice")
 
 
 def buffers_lib() -> C.CDLL:
@@ -273,6 +279,11 @@ def frame_append_lib() -> C.CDLL:
     return _extension("frame_append")
 
 
+def frame_splice_lib() -> C.CDLL:
+    """libsnappier_hip_frame_splice.so (include/snappier_hip_frame_splice.h)."""
+    return _extension("frame_splice")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -307,6 +318,10 @@ def frame_update_declared_symbols() -> list[str]:
 
 def frame_append_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_append"))
+
+
+def frame_splice_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_splice"))
 
 
 def status_string(st: int) -> str:

@@ -698,6 +698,77 @@ class BlockCodec:
                                                                      need[2], need[0])
         return new_len, status, new_index
 
+    def frame_splice_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", sp_off: torch.Tensor,
+                             sp_del: torch.Tensor, data: torch.Tensor, data_off: torch.Tensor, data_len: torch.Tensor, chunk_bytes: int,
+                             out: torch.Tensor, out_off: torch.Tensor, out_cap: torch.Tensor, max_slots: int, stage_cap: int,
+                             work: torch.Tensor | None = None, with_bound: bool = False):
+        """ONE splice per framed stream through its chunk index (snp_frame_splice_indexed_batch, libsnappier_hip_frame_splice.so):
+        -> (out_len, status, FrameIndex, result) and, with_bound, out_bound behind them.  The direct call: it enqueues only (it allocates its
+        outputs, and the workspace when `work` is None).
+
+        In what stream b decodes to, bytes [sp_off[b], sp_off[b] + sp_del[b]) are replaced by data[data_off[b] .. +data_len[b]) (int64 tensors,
+        read as unsigned): insert is sp_del 0, delete is data_len 0, truncate is sp_del = total - sp_off, and a stream with both 0 is left
+        alone.  The new stream of b goes to out[out_off[b] .. +out_cap[b]): the chunks around the hole are decoded and compressed again in
+        pieces of chunk_bytes, every other kept byte is a copy, and a stream is spliced whole or not at all (out_len[b] = 0 then:
+        include/snappier_hip_frame_splice.h).  The returned FrameIndex is the batch's index after the call (start / pos hold index.nentries +
+        max_slots rows; the old rows for a stream that is not written) and goes straight into frame_read_indexed, frame_write_indexed,
+        frame_append_indexed and the next splice.  result is the 4-element int64 d_result: [0] = chunk slots needed, [1] = sum of out_len over
+        the written streams, [2] = staging bytes needed, [3] = streams written; max_slots = stage_cap = 0 is the sizing call."""
+        if not 1 <= chunk_bytes <= N.BLOCK_SIZE:
+            raise ValueError(f"frame_splice_indexed: chunk_bytes = {chunk_bytes}, must be 1 .. {N.BLOCK_SIZE}")
+        self._bind()
+        ns = in_len.numel()
+        SL = N.frame_splice_lib()
+        framed, out, data = self._readable(framed, ns), self._readable(out, ns), self._readable(data, ns)
+        ne = index.nentries
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+        out_len = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        status = torch.zeros(ns, dtype=torch.int32, device=self.device)
+        first = torch.zeros(ns + 1, dtype=torch.int64, device=self.device)
+        rows = ne + max_slots
+        new_start = torch.empty(max(rows, 1), dtype=torch.int64, device=self.device)
+        new_pos = torch.empty(max(rows, 1), dtype=torch.int64, device=self.device)
+        total = torch.empty(ns, dtype=torch.int64, device=self.device)
+        tail = torch.empty(ns, dtype=torch.int32, device=self.device)
+        bound = torch.zeros(ns, dtype=torch.int64, device=self.device) if with_bound else None
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        w = self._work("frame_splice_indexed", work, SL.snp_frame_splice_indexed_workspace, ns, max_slots, stage_cap, chunk_bytes)
+        st = SL.snp_frame_splice_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                               _p(index.total), _p(index.tail), ne, _p(data), _p(sp_off), _p(sp_del), _p(data_len), _p(data_off),
+                                               chunk_bytes, max_slots, stage_cap, _p(out), _p(out_off), _p(out_cap), _p(out_len), _p(status),
+                                               _p(first), _p(new_start), _p(new_pos), _p(total), _p(tail), _p(bound), _p(w), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        got = (out_len, status, FrameIndex(first, new_start[:rows], new_pos[:rows], total, tail, result), result)
+        return got + (bound,) if with_bound else got
+
+    def frame_splice_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", sp_off: torch.Tensor,
+                               sp_del: torch.Tensor, data: torch.Tensor, data_off: torch.Tensor, data_len: torch.Tensor,
+                               chunk_bytes: int = N.BLOCK_SIZE, align: int = 1, max_bytes: int | None = None):
+        """Splice framed streams given the framed tensor, its table, its index and one splice per stream:
+        -> (out, out_off, out_len, status, FrameIndex).
+
+        ONE sizing call (max_slots = stage_cap = 0, every out_cap 0) that also asks for each named stream's size bound, ONE synchronising read
+        of its result and of the arena size (ValueError if that is above max_bytes), an arena in which stream b's slot is its bound rounded up
+        to `align` (0 for a stream that is left alone or refused), then the splice.  Streams with out_len 0 are not in the arena: the caller
+        keeps their old bytes, and the returned index holds their old rows."""
+        ns = in_len.numel()
+        zero = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        empty = torch.empty(0, dtype=torch.uint8, device=self.device)
+        _, _, _, result, bound = self.frame_splice_indexed(framed, in_off, in_len, index, sp_off, sp_del, data, data_off, data_len, chunk_bytes,
+                                                           empty, zero, zero, 0, 0, with_bound=True)
+        slot = (bound + (align - 1)) // align * align
+        ends = torch.cumsum(slot, 0)
+        out_off = ends - slot
+        need = torch.cat([result, ends[-1:] if ns else zero[:0].new_zeros(1)]).tolist()
+        if need[0] > 0xFFFFFFFF:
+            raise ValueError(f"frame_splice_to_memory: {need[0]} chunk slots, one call takes 2^32 - 1")
+        if max_bytes is not None and need[-1] > max_bytes:
+            raise ValueError(f"frame_splice_to_memory: the new streams take up to {need[-1]} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need[-1], 1), dtype=torch.uint8, device=self.device)
+        out_len, status, new_index, _ = self.frame_splice_indexed(framed, in_off, in_len, index, sp_off, sp_del, data, data_off, data_len,
+                                                                  chunk_bytes, out, out_off, bound, need[0], need[2])
+        return out[:need[-1]], out_off, out_len, status, new_index
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()
