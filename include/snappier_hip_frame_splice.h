@@ -52,8 +52,8 @@ extern "C" {
  *     snp_frame_append_indexed_batch fills up);
  *   - a splice whose lo and hi are multiples of c and whose ins is a multiple of c (or hi == total) equals that call's output for the edited
  *     buffer;
- *   - any other splice decodes to the edited buffer and may leave short chunks in the middle.  Fragmentation after many edits is accepted; a
- *     rechunk call is not part of this library.
+ *   - any other splice decodes to the edited buffer and may leave short chunks in the middle.  Fragmentation after many edits is accepted:
+ *     snp_frame_rechunk_indexed_batch (snappier_hip_frame_rechunk.h) brings a stream back to the chunked encoder's output.
  *
  * The new index.  new_first[nstreams + 1], new_total[nstreams] and new_tail[nstreams] are per stream; new_start and new_pos hold
  * nentries + max_slots rows each (both numbers are the host's, so the rows need no bound of their own).  For a written stream: its rows

@@ -22,6 +22,7 @@ HEADER_PATH = os.path.join(HERE, "..", "include", "snappier_hip.h")
 HASH_CRC32C, HASH_MUL = 0, 1
 BLOCK_SIZE = 65536
 MAX_BLOCK_COMPRESSED = 76491
+RECHUNK_REWRITE_ALL = 1                  # SNP_RECHUNK_REWRITE_ALL (include/snappier_hip_frame_rechunk.h)
 # snp_option (include/snappier_hip.h)
 (OPT_DECODE_LAYOUT, OPT_SMALL_BLOCK_MAX, OPT_SMALL_BLOCK_MIN_BATCH, OPT_COMPRESS_LAYOUT, OPT_COMPRESS_WINDOW_MAX_BATCH,
  OPT_TABLE_PROBE_TRIES, OPT_TABLE_PROBE_MAX_BYTES, OPT_PARALLEL_DECODE_MIN, OPT_FENCED, OPT_DECODE_LEFTOVERS, OPT_CRC_KERNEL,
@@ -188,6 +189,11 @@ _EXTENSIONS = {
         "snp_frame_splice_indexed_workspace": (_u64, [_u32, _u32, _u64, _u32]),
         "snp_frame_splice_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u64,
                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch rechunk of seekable framed streams to canonical form: clean chunks copied, the other pieces decoded and compressed again, the new index
+    "frame_rechunk": ("libsnappier_hip_frame_rechunk.so", "snappier_hip_frame_rechunk.h", {
+        "snp_frame_rechunk_indexed_workspace": (_u64, [_u32, _u32, _u64, _u32, _u32]),
+        "snp_frame_rechunk_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32,
+                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -232,6 +238,7 @@ FRAME_CHUNKED_PATH = _extension_path("frame_chunked")
 FRAME_UPDATE_PATH = _extension_path("frame_update")
 FRAME_APPEND_PATH = _extension_path("frame_append")
 FRAME_SPLICE_PATH = _extension_path("frame_splice")
+FRAME_RECHUNK_PATH = _extension_path("frame_rechunk")
 
 
 def buffers_lib() -> C.CDLL:
@@ -284,6 +291,11 @@ def frame_splice_lib() -> C.CDLL:
     return _extension("frame_splice")
 
 
+def frame_rechunk_lib() -> C.CDLL:
+    """libsnappier_hip_frame_rechunk.so (include/snappier_hip_frame_rechunk.h)."""
+    return _extension("frame_rechunk")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -322,6 +334,10 @@ def frame_append_declared_symbols() -> list[str]:
 
 def frame_splice_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_splice"))
+
+
+def frame_rechunk_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_rechunk"))
 
 
 def status_string(st: int) -> str:

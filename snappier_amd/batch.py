@@ -769,6 +769,73 @@ class BlockCodec:
                                                                   chunk_bytes, out, out_off, bound, need[0], need[2])
         return out[:need[-1]], out_off, out_len, status, new_index
 
+    def frame_rechunk_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", chunk_bytes: int,
+                              out: torch.Tensor, out_off: torch.Tensor, out_cap: torch.Tensor, max_slots: int, stage_cap: int, max_entries: int,
+                              rewrite_all: bool = False, work: torch.Tensor | None = None, with_bound: bool = False):
+        """Framed streams brought to canonical form through their chunk index (snp_frame_rechunk_indexed_batch,
+        libsnappier_hip_frame_rechunk.so): -> (out_len, status, FrameIndex, result) and, with_bound, out_bound behind them.  The direct call: it
+        enqueues only (it allocates its outputs, and the workspace when `work` is None).
+
+        The new stream of b goes to out[out_off[b] .. +out_cap[b]) and is what frame_encode_seekable writes for the stream's decoded bytes with
+        chunk_bytes: an old chunk that already is a piece of it is copied, the other pieces are decoded and compressed again; skippable, padding
+        and repeated-identifier chunks are dropped.  rewrite_all decodes, verifies and compresses every chunk.  A stream that is canonical already
+        is left alone (SNP_OK, out_len[b] = 0, its old rows), and a stream is rechunked whole or not at all (out_len[b] = 0 then:
+        include/snappier_hip_frame_rechunk.h).  The returned FrameIndex is the batch's index after the call (start / pos hold max_entries rows)
+        and goes straight into the read, update, append and splice calls and the next rechunk.  result is the 6-element int64 d_result:
+        [0] = decode rows / chunk slots needed, [1] = sum of out_len, [2] = staging bytes needed, [3] = streams written, [4] = rows of the new
+        index needed, [5] = streams left alone; max_slots = stage_cap = 0 is the sizing call."""
+        if not 1 <= chunk_bytes <= N.BLOCK_SIZE:
+            raise ValueError(f"frame_rechunk_indexed: chunk_bytes = {chunk_bytes}, must be 1 .. {N.BLOCK_SIZE}")
+        self._bind()
+        ns = in_len.numel()
+        RL = N.frame_rechunk_lib()
+        framed, out = self._readable(framed, ns), self._readable(out, ns)
+        ne = index.nentries
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+        out_len = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        status = torch.zeros(ns, dtype=torch.int32, device=self.device)
+        first = torch.zeros(ns + 1, dtype=torch.int64, device=self.device)
+        new_start = torch.empty(max(max_entries, 1), dtype=torch.int64, device=self.device)
+        new_pos = torch.empty(max(max_entries, 1), dtype=torch.int64, device=self.device)
+        total = torch.empty(ns, dtype=torch.int64, device=self.device)
+        tail = torch.empty(ns, dtype=torch.int32, device=self.device)
+        bound = torch.zeros(ns, dtype=torch.int64, device=self.device) if with_bound else None
+        result = torch.empty(6, dtype=torch.int64, device=self.device)
+        w = self._work("frame_rechunk_indexed", work, RL.snp_frame_rechunk_indexed_workspace, ns, max_slots, stage_cap, chunk_bytes, max_entries)
+        st = RL.snp_frame_rechunk_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                                _p(index.total), _p(index.tail), ne, chunk_bytes, N.RECHUNK_REWRITE_ALL if rewrite_all else 0,
+                                                max_slots, stage_cap, max_entries, _p(out), _p(out_off), _p(out_cap), _p(out_len), _p(status),
+                                                _p(first), _p(new_start), _p(new_pos), _p(total), _p(tail), _p(bound), _p(w), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        got = (out_len, status, FrameIndex(first, new_start[:max_entries], new_pos[:max_entries], total, tail, result), result)
+        return got + (bound,) if with_bound else got
+
+    def frame_rechunk_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", chunk_bytes: int,
+                                rewrite_all: bool = False, align: int = 1, max_bytes: int | None = None):
+        """Rechunk framed streams given the framed tensor, its table and its index: -> (out, out_off, out_len, status, FrameIndex).
+
+        ONE sizing call (max_slots = stage_cap = max_entries = 0, every out_cap 0) that also asks for each stream's size bound, ONE synchronising
+        read of its result and of the arena size (ValueError if that is above max_bytes), an arena in which stream b's slot is its bound rounded
+        up to `align` (0 for a stream that is left alone or refused), then the rechunk.  Streams with out_len 0 -- those that were canonical
+        already among them -- are not in the arena: the caller keeps their old bytes, and the returned index holds their old rows."""
+        ns = in_len.numel()
+        zero = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        empty = torch.empty(0, dtype=torch.uint8, device=self.device)
+        _, _, _, result, bound = self.frame_rechunk_indexed(framed, in_off, in_len, index, chunk_bytes, empty, zero, zero, 0, 0, 0, rewrite_all,
+                                                            with_bound=True)
+        slot = (bound + (align - 1)) // align * align
+        ends = torch.cumsum(slot, 0)
+        out_off = ends - slot
+        need = torch.cat([result, ends[-1:] if ns else zero[:0].new_zeros(1)]).tolist()
+        if need[0] > 0xFFFFFFFF or need[4] > 0xFFFFFFFF:
+            raise ValueError(f"frame_rechunk_to_memory: {need[0]} chunk slots and {need[4]} index rows, one call takes 2^32 - 1 of each")
+        if max_bytes is not None and need[-1] > max_bytes:
+            raise ValueError(f"frame_rechunk_to_memory: the new streams take up to {need[-1]} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need[-1], 1), dtype=torch.uint8, device=self.device)
+        out_len, status, new_index, _ = self.frame_rechunk_indexed(framed, in_off, in_len, index, chunk_bytes, out, out_off, bound, need[0], need[2],
+                                                                   need[4], rewrite_all)
+        return out[:need[-1]], out_off, out_len, status, new_index
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()

@@ -3,7 +3,7 @@
     python snappier_amd/build.py            # libsnappier_hip.so, libsnappier_hip_buffers.so, libsnappier_hip_buffers_decompress.so,
                                             # libsnappier_hip_frame_buffers.so, libsnappier_hip_layout.so, libsnappier_hip_frame_range.so,
                                             # libsnappier_hip_frame_index.so, libsnappier_hip_frame_chunked.so, libsnappier_hip_frame_update.so,
-                                            # libsnappier_hip_frame_append.so, libsnappier_hip_frame_splice.so
+                                            # libsnappier_hip_frame_append.so, libsnappier_hip_frame_splice.so, libsnappier_hip_frame_rechunk.so
                                             # (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
@@ -41,6 +41,8 @@ LIBS = {
     "libsnappier_hip_frame_append.so": ["frame_append.hip"],
     # include/snappier_hip_frame_splice.h: device batch splice (insert, delete, truncate) of seekable framed streams, with the new index -- the same kind of extension
     "libsnappier_hip_frame_splice.so": ["frame_splice.hip"],
+    # include/snappier_hip_frame_rechunk.h: device batch rechunk of seekable framed streams to canonical form, with the new index -- the same kind of extension
+    "libsnappier_hip_frame_rechunk.so": ["frame_rechunk.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 # every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)

@@ -84,6 +84,9 @@ __host__ __device__ inline IxPlan ix_plan(const FrameIndex& x, u32 nstreams, u32
     return k;
 }
 
+// The rule of a row [s, e) against the hop of the header it points at: a data chunk that decodes to exactly e - s bytes.
+__host__ __device__ __forceinline__ bool ix_row_holds(u64 s, u64 e, const Hop& h) { return e >= s && h.kind == HOP_DATA && e - s == h.dec; }
+
 // The check of row i of the stream (p, n): the header at pos[i] is re-read inside the stream's bytes and must be a data chunk that decodes to
 // exactly end - start bytes; an interior row must also lie inside [lo, hi).  *h: the hop (body_len, crc and type come from the header).
 __host__ __device__ inline bool ix_row_check(const FrameIndex& x, const u8* __restrict__ p, u64 n, const IxPlan& k, u64 i, bool interior, Hop* h)
@@ -91,7 +94,7 @@ __host__ __device__ inline bool ix_row_check(const FrameIndex& x, const u8* __re
     const u64 s = x.start[i], e = ix_row_end(x, k.f1, k.total, i), pos = x.pos[i];
     if (e < s || pos >= n) return false;
     *h = frame_hop(p, n, pos);
-    if (h->kind != HOP_DATA || e - s != h->dec) return false;
+    if (!ix_row_holds(s, e, *h)) return false;
     return !interior || (s >= k.lo && e <= k.hi);
 }
 
