@@ -194,6 +194,11 @@ _EXTENSIONS = {
         "snp_frame_rechunk_indexed_workspace": (_u64, [_u32, _u32, _u64, _u32, _u32]),
         "snp_frame_rechunk_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _u64, _u32,
                                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch compose: new seekable framed streams from windows of old ones -- chunks inside a window copied, the cut chunks decoded and compressed again, the new index
+    "frame_compose": ("libsnappier_hip_frame_compose.so", "snappier_hip_frame_compose.h", {
+        "snp_frame_compose_indexed_workspace": (_u64, [_u32, _u32, _u32, _u32, _u64, _u32, _u32]),
+        "snp_frame_compose_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32,
+                                                   _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -239,6 +244,7 @@ FRAME_UPDATE_PATH = _extension_path("frame_update")
 FRAME_APPEND_PATH = _extension_path("frame_append")
 FRAME_SPLICE_PATH = _extension_path("frame_splice")
 FRAME_RECHUNK_PATH = _extension_path("frame_rechunk")
+FRAME_COMPOSE_PATH = _extension_path("frame_compose")
 
 
 def buffers_lib() -> C.CDLL:
@@ -296,6 +302,11 @@ def frame_rechunk_lib() -> C.CDLL:
     return _extension("frame_rechunk")
 
 
+def frame_compose_lib() -> C.CDLL:
+    """libsnappier_hip_frame_compose.so (include/snappier_hip_frame_compose.h)."""
+    return _extension("frame_compose")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -338,6 +349,10 @@ def frame_splice_declared_symbols() -> list[str]:
 
 def frame_rechunk_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_rechunk"))
+
+
+def frame_compose_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_compose"))
 
 
 def status_string(st: int) -> str:

@@ -836,6 +836,79 @@ class BlockCodec:
                                                                    need[4], rewrite_all)
         return out[:need[-1]], out_off, out_len, status, new_index
 
+    def frame_compose_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", chunk_bytes: int,
+                              out: torch.Tensor, out_off: torch.Tensor, out_cap: torch.Tensor, max_slots: int, stage_cap: int, max_entries: int,
+                              seg_first: torch.Tensor, seg_stream: torch.Tensor, seg_off: torch.Tensor, seg_len: torch.Tensor,
+                              work: torch.Tensor | None = None, with_bound: bool = False):
+        """New framed streams made of windows of old ones through the old streams' chunk index (snp_frame_compose_indexed_batch,
+        libsnappier_hip_frame_compose.so): -> (out_len, status, FrameIndex, result) and, with_bound, out_bound behind them.  The direct call: it
+        enqueues only (it allocates its outputs, and the workspace when `work` is None).
+
+        Output j is the segments [seg_first[j], seg_first[j + 1]) one behind the other (seg_first: int64, nout + 1 values); segment g is the
+        decoded bytes [seg_off[g], seg_off[g] + seg_len[g]) of stream seg_stream[g] (int32).  It goes to out[out_off[j] .. +out_cap[j]): the
+        chunks that lie inside a segment are copied, the chunk a segment cuts at its head or tail is decoded and the part inside compressed
+        again in pieces of chunk_bytes; skippable, padding and repeated-identifier chunks are dropped.  An output is composed whole or not at
+        all (out_len[j] = 0 then: include/snappier_hip_frame_compose.h).  The returned FrameIndex is the index of the OUTPUTS (start / pos hold
+        max_entries rows) and goes straight into the read, update, append, splice and rechunk calls and the next compose.  result is the
+        6-element int64 d_result: [0] = decode rows / chunk slots needed, [1] = sum of out_len, [2] = staging bytes needed, [3] = outputs
+        written, [4] = rows of the new index needed, [5] = kept chunks copied; max_slots = stage_cap = 0 is the sizing call."""
+        if not 1 <= chunk_bytes <= N.BLOCK_SIZE:
+            raise ValueError(f"frame_compose_indexed: chunk_bytes = {chunk_bytes}, must be 1 .. {N.BLOCK_SIZE}")
+        self._bind()
+        ns, nout, nsegs = in_len.numel(), seg_first.numel() - 1, seg_stream.numel()
+        if nout < 0 or seg_off.numel() != nsegs or seg_len.numel() != nsegs:
+            raise ValueError("frame_compose_indexed: seg_first holds nout + 1 values; seg_stream, seg_off and seg_len one per segment")
+        CL = N.frame_compose_lib()
+        framed, out = self._readable(framed, ns), self._readable(out, nout)
+        ne = index.nentries
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+        out_len = torch.zeros(nout, dtype=torch.int64, device=self.device)
+        status = torch.zeros(nout, dtype=torch.int32, device=self.device)
+        first = torch.zeros(nout + 1, dtype=torch.int64, device=self.device)
+        new_start = torch.empty(max(max_entries, 1), dtype=torch.int64, device=self.device)
+        new_pos = torch.empty(max(max_entries, 1), dtype=torch.int64, device=self.device)
+        total = torch.zeros(nout, dtype=torch.int64, device=self.device)
+        tail = torch.zeros(nout, dtype=torch.int32, device=self.device)
+        bound = torch.zeros(nout, dtype=torch.int64, device=self.device) if with_bound else None
+        result = torch.empty(6, dtype=torch.int64, device=self.device)
+        w = self._work("frame_compose_indexed", work, CL.snp_frame_compose_indexed_workspace, ns, nout, nsegs, max_slots, stage_cap, chunk_bytes,
+                       max_entries)
+        st = CL.snp_frame_compose_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                                _p(index.total), _p(index.tail), ne, _p(seg_first), _p(seg_stream), _p(seg_off), _p(seg_len), nout,
+                                                nsegs, chunk_bytes, max_slots, stage_cap, max_entries, _p(out), _p(out_off), _p(out_cap),
+                                                _p(out_len), _p(status), _p(first), _p(new_start), _p(new_pos), _p(total), _p(tail), _p(bound),
+                                                _p(w), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        got = (out_len, status, FrameIndex(first, new_start[:max_entries], new_pos[:max_entries], total, tail, result), result)
+        return got + (bound,) if with_bound else got
+
+    def frame_compose_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex",
+                                seg_first: torch.Tensor, seg_stream: torch.Tensor, seg_off: torch.Tensor, seg_len: torch.Tensor,
+                                chunk_bytes: int = N.BLOCK_SIZE, align: int = 1, max_bytes: int | None = None):
+        """Compose new framed streams given the framed tensor, its table, its index and the segment list:
+        -> (out, out_off, out_len, status, FrameIndex).
+
+        ONE sizing call (max_slots = stage_cap = max_entries = 0, every out_cap 0) that also asks for each output's size bound, ONE
+        synchronising read of its result and of the arena size (ValueError if that is above max_bytes), an arena in which output j's slot is its
+        bound rounded up to `align` (0 for an output that is refused), then the compose.  The returned index is the outputs'."""
+        nout = seg_first.numel() - 1
+        zero = torch.zeros(max(nout, 0), dtype=torch.int64, device=self.device)
+        empty = torch.empty(0, dtype=torch.uint8, device=self.device)
+        _, _, _, result, bound = self.frame_compose_indexed(framed, in_off, in_len, index, chunk_bytes, empty, zero, zero, 0, 0, 0, seg_first,
+                                                            seg_stream, seg_off, seg_len, with_bound=True)
+        slot = (bound + (align - 1)) // align * align
+        ends = torch.cumsum(slot, 0)
+        out_off = ends - slot
+        need = torch.cat([result, ends[-1:] if nout else zero[:0].new_zeros(1)]).tolist()
+        if need[0] > 0xFFFFFFFF or need[4] > 0xFFFFFFFF:
+            raise ValueError(f"frame_compose_to_memory: {need[0]} chunk slots and {need[4]} index rows, one call takes 2^32 - 1 of each")
+        if max_bytes is not None and need[-1] > max_bytes:
+            raise ValueError(f"frame_compose_to_memory: the new streams take up to {need[-1]} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need[-1], 1), dtype=torch.uint8, device=self.device)
+        out_len, status, new_index, _ = self.frame_compose_indexed(framed, in_off, in_len, index, chunk_bytes, out, out_off, bound, need[0], need[2],
+                                                                   need[4], seg_first, seg_stream, seg_off, seg_len)
+        return out[:need[-1]], out_off, out_len, status, new_index
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()
