@@ -7,7 +7,7 @@ include/snappier_hip.h.  Importing it requires the built libsnappier_hip.so -- t
 from ._native import (BLOCK_SIZE, HASH_CRC32C, HASH_MUL, MAX_BLOCK_COMPRESSED, lib, status_string)  # noqa: F401
 from .context import Context, default_context  # noqa: F401
 from .errors import InsufficientBufferException, InvalidDataException, InvalidOperationException  # noqa: F401
-from .snappy import Snappy, crc32c, frame_decode, frame_encode  # noqa: F401
+from .snappy import Snappy, crc32c, crc32c_combine, frame_decode, frame_encode  # noqa: F401
 from .stream import CompressionMode, SnappyStream  # noqa: F401
 from .multidevice import MultiDeviceCodec  # noqa: F401
 

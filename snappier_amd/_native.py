@@ -199,6 +199,12 @@ _EXTENSIONS = {
         "snp_frame_compose_indexed_workspace": (_u64, [_u32, _u32, _u32, _u32, _u64, _u32, _u32]),
         "snp_frame_compose_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32,
                                                    _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch digest: CRC-32C of windows of what seekable framed streams decode to, combined from the chunk headers' CRCs -- only the cut chunks are decoded
+    "frame_digest": ("libsnappier_hip_frame_digest.so", "snappier_hip_frame_digest.h", {
+        "snp_frame_digest_indexed_workspace": (_u64, [_u32, _u64]),
+        "snp_frame_digest_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u64,
+                                                  _vp, _vp, _vp, _vp, _vp]),
+        "snp_crc32c_combine": (_u32, [_u32, _u32, _u64])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -245,6 +251,7 @@ FRAME_APPEND_PATH = _extension_path("frame_append")
 FRAME_SPLICE_PATH = _extension_path("frame_splice")
 FRAME_RECHUNK_PATH = _extension_path("frame_rechunk")
 FRAME_COMPOSE_PATH = _extension_path("frame_compose")
+FRAME_DIGEST_PATH = _extension_path("frame_digest")
 
 
 def buffers_lib() -> C.CDLL:
@@ -307,6 +314,11 @@ def frame_compose_lib() -> C.CDLL:
     return _extension("frame_compose")
 
 
+def frame_digest_lib() -> C.CDLL:
+    """libsnappier_hip_frame_digest.so (include/snappier_hip_frame_digest.h)."""
+    return _extension("frame_digest")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -353,6 +365,10 @@ def frame_rechunk_declared_symbols() -> list[str]:
 
 def frame_compose_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_compose"))
+
+
+def frame_digest_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_digest"))
 
 
 def status_string(st: int) -> str:

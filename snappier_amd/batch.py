@@ -909,6 +909,54 @@ class BlockCodec:
                                                                    need[4], seg_first, seg_stream, seg_off, seg_len)
         return out[:need[-1]], out_off, out_len, status, new_index
 
+    def frame_digest_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", req_stream: torch.Tensor,
+                             req_off: torch.Tensor, req_len: torch.Tensor, edge_cap: int | None = None, work: torch.Tensor | None = None):
+        """The CRC-32C of any number of windows of what framed streams decode to, from the CRCs their chunk headers carry, with no decode of
+        the chunks inside a window (snp_frame_digest_indexed_batch, libsnappier_hip_frame_digest.so): -> (digest, dig_len, status, result).
+
+        Request r names stream req_stream[r] (int32) and the window [req_off[r], req_off[r] + req_len[r]) of what it decodes to (int64
+        tensors, read as unsigned; req_off 0 and req_len -1 is the whole stream).  digest (int32, the bits of the unsigned plain CRC-32C) and
+        dig_len (int64) are those of the clipped window; status is what frame_read_indexed gives for the same request.  The digest does not
+        depend on how the stream is chunked.  A corrupt BODY of a chunk inside a window is not noticed: only the chunks a window cuts are decoded
+        (include/snappier_hip_frame_digest.h).  result is the 4-element int64 d_result: [0] = interior rows combined, [1] = sum of dig_len over
+        the OK requests, [2] = edge scratch bytes needed, [3] = requests that are OK.  Default edge_cap: a first call with 0, then a
+        synchronising read of its d_result, and no second call if nothing more is needed.  A caller that passes edge_cap and work enqueues only."""
+        self._bind()
+        nreq, ns = req_stream.numel(), in_len.numel()
+        if req_stream.dtype != torch.int32:
+            raise ValueError("frame_digest_indexed: req_stream must be an int32 tensor")
+        DL = N.frame_digest_lib()
+        framed = self._readable(framed, nreq)
+        digest = torch.empty(nreq, dtype=torch.int32, device=self.device)
+        dig_len = torch.empty(nreq, dtype=torch.int64, device=self.device)
+        status = torch.empty(nreq, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+
+        def call(ec: int, w: torch.Tensor | None):
+            w = self._work("frame_digest_indexed", w, DL.snp_frame_digest_indexed_workspace, nreq, ec)
+            st = DL.snp_frame_digest_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                                   _p(index.total), _p(index.tail), index.nentries, _p(req_stream), _p(req_off), _p(req_len), nreq,
+                                                   ec, _p(digest), _p(dig_len), _p(status), _p(w), _p(result))
+            raise_for_status(st, self.ctx.handle)
+
+        if edge_cap is None:
+            call(0, None)
+            edge_cap = result.tolist()[2]
+            if edge_cap == 0:
+                return digest, dig_len, status, result
+        call(edge_cap, work)
+        return digest, dig_len, status, result
+
+    def frame_digest_streams(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex"):
+        """The CRC-32C of everything each stream decodes to: -> (digest, dig_len, status), one per stream.  A whole stream cuts no chunk, so
+        nothing is decoded (edge_cap = 0) and nothing synchronises: one header read and one multiplication per chunk."""
+        ns = in_len.numel()
+        req_stream = torch.arange(ns, dtype=torch.int32, device=self.device)
+        req_off = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        req_len = torch.full((ns,), -1, dtype=torch.int64, device=self.device)
+        return self.frame_digest_indexed(framed, in_off, in_len, index, req_stream, req_off, req_len, edge_cap=0)[:3]
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()

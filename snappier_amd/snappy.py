@@ -114,6 +114,12 @@ def crc32c(data, masked: bool = False, ctx: Context | None = None) -> int:
     return v.value
 
 
+def crc32c_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """The plain (unmasked) CRC-32C of A || B from the plain CRC-32Cs of A and of B and B's length in bytes (snp_crc32c_combine,
+    libsnappier_hip_frame_digest.so): host arithmetic, no context and no device."""
+    return N.frame_digest_lib().snp_crc32c_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, len_b)
+
+
 def frame_encode(data, ctx: Context | None = None) -> bytes:
     """Whole-buffer SnappyStream compress: stream identifier + one chunk per 64 KiB (SnappyStreamCompressor.cs)."""
     ctx = ctx or default_context()
