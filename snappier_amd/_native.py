@@ -23,6 +23,7 @@ HASH_CRC32C, HASH_MUL = 0, 1
 BLOCK_SIZE = 65536
 MAX_BLOCK_COMPRESSED = 76491
 RECHUNK_REWRITE_ALL = 1                  # SNP_RECHUNK_REWRITE_ALL (include/snappier_hip_frame_rechunk.h)
+DIFF_PREFIX, DIFF_SUFFIX, DIFF_EXACT = 1, 2, 4   # SNP_DIFF_PREFIX, SNP_DIFF_SUFFIX, SNP_DIFF_EXACT (include/snappier_hip_frame_diff.h)
 # snp_option (include/snappier_hip.h)
 (OPT_DECODE_LAYOUT, OPT_SMALL_BLOCK_MAX, OPT_SMALL_BLOCK_MIN_BATCH, OPT_COMPRESS_LAYOUT, OPT_COMPRESS_WINDOW_MAX_BATCH,
  OPT_TABLE_PROBE_TRIES, OPT_TABLE_PROBE_MAX_BYTES, OPT_PARALLEL_DECODE_MIN, OPT_FENCED, OPT_DECODE_LEFTOVERS, OPT_CRC_KERNEL,
@@ -205,6 +206,11 @@ _EXTENSIONS = {
         "snp_frame_digest_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u64,
                                                   _vp, _vp, _vp, _vp, _vp]),
         "snp_crc32c_combine": (_u32, [_u32, _u32, _u64])}),
+    # device batch diff: longest common prefix and suffix of pairs of windows of what seekable framed streams decode to -- spans between common chunk boundaries compared by header CRC
+    "frame_diff": ("libsnappier_hip_frame_diff.so", "snappier_hip_frame_diff.h", {
+        "snp_frame_diff_indexed_workspace": (_u64, [_u32, _u64, _u64]),
+        "snp_frame_diff_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -252,6 +258,7 @@ FRAME_SPLICE_PATH = _extension_path("frame_splice")
 FRAME_RECHUNK_PATH = _extension_path("frame_rechunk")
 FRAME_COMPOSE_PATH = _extension_path("frame_compose")
 FRAME_DIGEST_PATH = _extension_path("frame_digest")
+FRAME_DIFF_PATH = _extension_path("frame_diff")
 
 
 def buffers_lib() -> C.CDLL:
@@ -319,6 +326,11 @@ def frame_digest_lib() -> C.CDLL:
     return _extension("frame_digest")
 
 
+def frame_diff_lib() -> C.CDLL:
+    """libsnappier_hip_frame_diff.so (include/snappier_hip_frame_diff.h)."""
+    return _extension("frame_diff")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -369,6 +381,10 @@ def frame_compose_declared_symbols() -> list[str]:
 
 def frame_digest_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_digest"))
+
+
+def frame_diff_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_diff"))
 
 
 def status_string(st: int) -> str:

@@ -12,6 +12,8 @@ from . import _native as N
 from .context import Context
 from .errors import raise_for_status
 
+DIFF_PREFIX, DIFF_SUFFIX, DIFF_EXACT = N.DIFF_PREFIX, N.DIFF_SUFFIX, N.DIFF_EXACT   # the flags of BlockCodec.frame_diff_indexed
+
 
 def _p(t: torch.Tensor | None):
     return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(None)
@@ -956,6 +958,88 @@ class BlockCodec:
         req_off = torch.zeros(ns, dtype=torch.int64, device=self.device)
         req_len = torch.full((ns,), -1, dtype=torch.int64, device=self.device)
         return self.frame_digest_indexed(framed, in_off, in_len, index, req_stream, req_off, req_len, edge_cap=0)[:3]
+
+    def frame_diff_indexed(self, a, b, req_stream_a: torch.Tensor, req_off_a: torch.Tensor, req_len_a: torch.Tensor, req_stream_b: torch.Tensor,
+                           req_off_b: torch.Tensor, req_len_b: torch.Tensor, flags: int = DIFF_PREFIX | DIFF_SUFFIX, max_rows: int | None = None,
+                           scratch_cap: int | None = None, work: torch.Tensor | None = None):
+        """The longest common prefix and suffix of pairs of windows of what framed streams decode to (snp_frame_diff_indexed_batch,
+        libsnappier_hip_frame_diff.so): -> (prefix, suffix, len_a, len_b, status, result).
+
+        a and b are the two sides, each (framed, in_off, in_len, FrameIndex); the same tuple may be passed twice.  Request r compares the
+        window [req_off_a[r], +req_len_a[r]) of stream req_stream_a[r] (int32) of side a with its counterpart on side b (int64 tensors, read as
+        unsigned; offset 0 and length -1 is the whole stream).  len_a, len_b are the clipped lengths, prefix and suffix (int64) the common
+        bytes at the windows' starts and ends; with both flags they never overlap, and (off = prefix, del = len_a - prefix - suffix,
+        ins = b[prefix, len_b - suffix)) is a splice that turns window a into window b.  Spans between chunk boundaries both streams share are
+        compared by the CRCs in their chunk headers and are not decoded: a corrupt BODY there is not noticed, and two different spans whose
+        CRCs collide (2^-32 per span) are taken as equal, unless flags has DIFF_EXACT (include/snappier_hip_frame_diff.h).  result is the
+        4-element int64 d_result: [0] = rows needed, [1] = sum of min(len_a, len_b) over the OK requests, [2] = scratch bytes needed,
+        [3] = requests that are OK.  Default bounds: the two sizing rounds (max_rows = 0, then scratch_cap = 0), each with a synchronising read
+        of d_result, then the real call unless a sizing round already was one.  A caller that passes both bounds and work enqueues only."""
+        self._bind()
+        nreq = req_stream_a.numel()
+        if req_stream_a.dtype != torch.int32 or req_stream_b.dtype != torch.int32:
+            raise ValueError("frame_diff_indexed: req_stream_a and req_stream_b must be int32 tensors")
+        DL = N.frame_diff_lib()
+        sides = []
+        for framed, in_off, in_len, index in (a, b):
+            ns = in_len.numel()
+            framed = self._readable(framed, nreq)
+            start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+            sides.append((framed, in_off, in_len, start, pos, index))
+        prefix, suffix, len_a, len_b = (torch.empty(nreq, dtype=torch.int64, device=self.device) for _ in range(4))
+        status = torch.empty(nreq, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+
+        def call(mr: int, sc: int, w: torch.Tensor | None):
+            w = self._work("frame_diff_indexed", w, DL.snp_frame_diff_indexed_workspace, nreq, mr, sc)
+            args = []
+            for framed, in_off, in_len, start, pos, index in sides:
+                args += [_p(framed), _p(in_off), _p(in_len), in_len.numel(), _p(index.first), _p(start), _p(pos), _p(index.total), _p(index.tail),
+                         index.nentries]
+            st = DL.snp_frame_diff_indexed_batch(self.ctx.handle, *args, _p(req_stream_a), _p(req_off_a), _p(req_len_a), _p(req_stream_b),
+                                                 _p(req_off_b), _p(req_len_b), nreq, flags, mr, sc, _p(len_a), _p(len_b), _p(prefix), _p(suffix),
+                                                 _p(status), _p(w), _p(result))
+            raise_for_status(st, self.ctx.handle)
+
+        sized = False
+        if max_rows is None:
+            call(0, 0 if scratch_cap is None else scratch_cap, None)
+            max_rows = result.tolist()[0]
+            sized = max_rows == 0
+        if scratch_cap is None:
+            if not sized:
+                call(max_rows, 0, None)
+            scratch_cap = result.tolist()[2]
+            sized = scratch_cap == 0
+        if not sized:
+            call(max_rows, scratch_cap, work)
+        return prefix, suffix, len_a, len_b, status, result
+
+    def frame_diff_streams(self, a, b, exact: bool = False):
+        """Stream i of side a against stream i of side b, whole: -> (prefix, suffix, len_a, len_b, status), one per stream (the sides hold the
+        same number of streams).  Stream i of a equals stream i of b iff prefix == len_a == len_b."""
+        ns = a[2].numel()
+        if b[2].numel() != ns:
+            raise ValueError("frame_diff_streams: the two sides must hold the same number of streams")
+        req_stream = torch.arange(ns, dtype=torch.int32, device=self.device)
+        req_off = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        req_len = torch.full((ns,), -1, dtype=torch.int64, device=self.device)
+        flags = DIFF_PREFIX | DIFF_SUFFIX | (DIFF_EXACT if exact else 0)
+        return self.frame_diff_indexed(a, b, req_stream, req_off, req_len, req_stream, req_off, req_len, flags)[:5]
+
+    def frame_delta_streams(self, a, b):
+        """The one splice per stream that turns stream i of side a into stream i of side b: -> (off, del, ins_off, ins_len, status), int64
+        tensors (status int32) -- replace bytes [off, off + del) of what a decodes to by bytes [ins_off, ins_off + ins_len) of what b decodes
+        to.  Equal streams give del = ins_len = 0.  A stream whose status is not OK gives zeros.  The repair of a from b in three calls:
+
+            off, dele, ins_off, ins_len, status = cd.frame_delta_streams(a, b)
+            data_off = torch.cumsum(ins_len, 0) - ins_len
+            data = torch.empty(int(ins_len.sum()), dtype=torch.uint8, device="cuda")
+            cd.frame_read_indexed(*b, req_stream, ins_off, ins_len, data, data_off, ins_len)          # req_stream = arange(nstreams)
+            cd.frame_splice_indexed(*a, off, dele, data, data_off, ins_len, chunk_bytes, out, out_off, out_cap, max_slots, stage_cap)
+        """
+        prefix, suffix, len_a, len_b, status = self.frame_diff_streams(a, b)
+        return prefix, len_a - prefix - suffix, prefix.clone(), len_b - prefix - suffix, status
 
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()

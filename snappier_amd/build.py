@@ -4,7 +4,8 @@
                                             # libsnappier_hip_frame_buffers.so, libsnappier_hip_layout.so, libsnappier_hip_frame_range.so,
                                             # libsnappier_hip_frame_index.so, libsnappier_hip_frame_chunked.so, libsnappier_hip_frame_update.so,
                                             # libsnappier_hip_frame_append.so, libsnappier_hip_frame_splice.so, libsnappier_hip_frame_rechunk.so,
-                                            # libsnappier_hip_frame_compose.so, libsnappier_hip_frame_digest.so
+                                            # libsnappier_hip_frame_compose.so, libsnappier_hip_frame_digest.so,
+                                            # libsnappier_hip_frame_diff.so
                                             # (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
@@ -48,6 +49,8 @@ LIBS = {
     "libsnappier_hip_frame_compose.so": ["frame_compose.hip"],
     # include/snappier_hip_frame_digest.h: device batch digest (CRC-32C of decoded windows) of seekable framed streams from their chunk headers, no decode -- the same kind of extension
     "libsnappier_hip_frame_digest.so": ["frame_digest.hip"],
+    # include/snappier_hip_frame_diff.h: device batch diff (common prefix and suffix of decoded windows) of seekable framed streams, header CRCs between common chunk boundaries -- the same kind of extension
+    "libsnappier_hip_frame_diff.so": ["frame_diff.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 # every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)
