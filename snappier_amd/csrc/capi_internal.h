@@ -9,8 +9,9 @@
 // are linked against libsnappier_hip.so and drive its contexts through this header; what they share among themselves is in work_carver.h,
 // scan_tiles.h, frame_hop_device.h (one hop of a framed stream's header walk, the per-span bodies, the span and chunk tables: shared with framing.hip,
 // frame_scan.hip and capi_frame.hip), frame_walk_device.h (the span walk over many streams), frame_edges_device.h (the edge chunks of a window:
-// range decode and indexed read), frame_index_device.h (the planning of one indexed request, host and device) and frame_chunked_device.h (the slot
-// arithmetic of the chunked frame encode, host and device).
+// range decode and indexed read), frame_index_device.h (the planning of one indexed request, host and device), frame_chunked_device.h (the slot
+// arithmetic of the chunked frame encode, host and device) and frame_rewrite_device.h (what the five calls that rewrite seekable streams share:
+// the slot table, its re-encode, the row verdict, the emit of a slot).
 // No codec arithmetic happens on the host: every byte of compress / decompress / CRC work is done by the gfx950 kernels in compress_lanes.hip,
 // compress_win.hip, decode_chains.hip, decompress.hip, decompress_small.hip, tag_index.hip, crc32c.hip, framing.hip, frame_scan.hip.
 // There is no CPU fallback -- without a HIP device snp_ctx_create fails with SNP_ERR_DEVICE.

@@ -19,8 +19,7 @@
 //   rows      one thread per new row: an old row copied, or a fresh chunk's row from the size scan; per stream: new_first, new_total, new_tail
 // Nothing here allocates, reads back or synchronises: the call is capturable like the other _batch entry points.
 #include "capi_internal.h"
-#include "scan_tiles.h"
-#include "work_carver.h"
+#include "frame_rewrite_device.h"
 #include "frame_append_device.h"
 #include "../../include/snappier_hip_frame_append.h"
 
@@ -28,8 +27,6 @@ namespace {
 
 constexpr u32 kAppend = 0x100u, kReopen = 0x200u, kIdent = 0x400u, kWritten = 0x800u;    // stream flags above the status byte
 constexpr u32 kOverlayGroups = 8192;                                // grid of the grid-stride overlay
-constexpr u32 kEmitGroups = 2048;                                   // ... of the emit: 8 workgroups per CU
-constexpr u32 kRowGroups = 1u << 20;                                // ... of the index merge
 
 struct ApArgs {
     u8* buf;
@@ -48,26 +45,7 @@ struct ApStreams {
     u32 *flags, *d, *fill;
     i32* fail;                                              // the status of a reopened tail that did not decode or verify
 };
-// per slot of either table: what the compressor, the CRC and the emit read
-struct ApSlots {
-    u64 *in_off, *coff;
-    u32 *len, *stream, *comp_len, *crc;
-    i32* c_status;
-};
-
-struct ScanWords {
-    const u64* __restrict__ src;
-    __device__ __forceinline__ u64 operator()(u64 i) const { return src[i]; }
-};
-struct ScanFramed {
-    const u32* __restrict__ len;
-    const u32* __restrict__ comp_len;
-    __device__ __forceinline__ u64 operator()(u64 i) const
-    {
-        bool shrink;
-        return len[i] ? SNP_CHUNK_HEADER_LEN + payload_of(comp_len[i], len[i], &shrink) : 0;
-    }
-};
+using ApSlots = RwOwnedSlots;                               // per slot of either table, tails and fresh
 
 // admission in stream order: both sums only grow
 struct Admit {
@@ -131,7 +109,7 @@ __global__ __launch_bounds__(256) void k_fa_fail(u32 max_tails, ChunkRows rows, 
 {
     const u32 t = blockIdx.x * 256u + threadIdx.x;
     if (t >= max_tails || rows.tag[t] == kNone) return;
-    const i32 s = rows.status[t] != SNP_OK ? rows.status[t] : rows.out_len[t] != rows.out_cap[t] ? SNP_ERR_INCOMPLETE : SNP_OK;
+    const i32 s = row_verdict(rows, t);
     if (s != SNP_OK) st.fail[tl.stream[t]] = s;
 }
 
@@ -217,17 +195,7 @@ __global__ __launch_bounds__(256) void k_fa_sizes(ApArgs a, ApStreams st, Admit 
     }
 }
 
-// [type:1][len:3 LE = payload + 4][masked crc:4 LE] of a chunk, by the first 8 threads of a team
-__device__ __forceinline__ void chunk_header(u8* at, u32 t, bool shrink, u32 pl, u32 crc)
-{
-    if (t < SNP_CHUNK_HEADER_LEN) {
-        const u32 bs = pl + 4;                                          // SnappyStreamCompressor.cs:236,251
-        const u32 v = t == 0 ? (shrink ? 0u : 1u) : t < 4 ? (bs >> (8 * (t - 1))) : (crc >> (8 * (t - 4)));
-        at[t] = static_cast<u8>(v);
-    }
-}
-
-// k_fc_emit's shape over both tables: a workgroup takes `group` consecutive slots of one table (64 KiB of input), its teams of `team` threads take them
+// The shape of fc_group and fc_team (frame_chunked_device.h) over both tables: a workgroup takes `group` consecutive slots of one table (64 KiB of input), its teams of `team` threads take them
 // in turn; units [0, tail_units) are the tail table's, the rest the fresh table's.  What steers a team is uniform over it; a chunk goes to its
 // stream at the cut (a reopened tail), or behind it where the size scan puts it (a fresh chunk; the first one of an empty stream brings the identifier).
 __global__ __launch_bounds__(256) void k_fa_emit(ApArgs a, ApStreams st, u32 max_tails, u32 max_slots, u32 group, u32 team, u64 tail_units, u64 units,
@@ -258,7 +226,7 @@ __global__ __launch_bounds__(256) void k_fa_emit(ApArgs a, ApStreams st, u32 max
                 if (!shrink) from = a.src + sl.in_off[c];
                 if (c == first && (st.flags[b] & kIdent) && t < SNP_STREAM_HEADER_LEN) stream[t] = k_fc_stream_id[t];   // EnsureStreamHeaderWritten  :148-157
             }
-            chunk_header(stream + pos, t, shrink, pl, sl.crc[c]);
+            chunk_header(stream + pos, t, shrink ? 0u : 1u, pl, sl.crc[c]);
             team_copy(stream + pos + SNP_CHUNK_HEADER_LEN, from, pl, t, team);
         }
     }
@@ -302,18 +270,6 @@ struct AppendWork {
     u8 *raw, *comp;
     u64 bytes;
 };
-ApSlots carve_slots(WorkCarver& k, u64 n)
-{
-    ApSlots s;
-    s.in_off = k.take<u64>(n);
-    s.coff = k.take<u64>(n);
-    s.len = k.take<u32>(n);
-    s.stream = k.take<u32>(n);
-    s.comp_len = k.take<u32>(n);
-    s.crc = k.take<u32>(n);
-    s.c_status = k.take<i32>(n);
-    return s;
-}
 AppendWork work_layout(void* base, u32 nstreams, u32 max_tails, u32 max_slots, u32 chunk_bytes)
 {
     AppendWork w{};
@@ -337,19 +293,17 @@ AppendWork work_layout(void* base, u32 nstreams, u32 max_tails, u32 max_slots, u
     w.st.d = k.take<u32>(ns);
     w.st.fill = k.take<u32>(ns);
     w.st.fail = k.take<i32>(ns);
-    w.tl = carve_slots(k, T);
-    w.fr = carve_slots(k, M);
+    w.tl = carve_rw_owned_slots(k, T);
+    w.fr = carve_rw_owned_slots(k, M);
     w.rows = carve_chunk_rows(k, T);
     w.cscan = k.take<u64>(M + 1);
     // raw staging: tail slot t at t * chunk_bytes (+ slack for the compressor's vector loads).  Compressed staging: the tail slots, then the fresh
-    // slots, at a stride of snp_comp_stride(chunk_bytes) as in frame_chunked.hip; the appended bytes themselves are never staged.
+    // slots, at a stride of snp_comp_stride(chunk_bytes) (fc_stage_off); the appended bytes themselves are never staged.
     w.raw = k.take<u8>(T * chunk_bytes + 256);
     w.comp = k.take<u8>((T + M) * snp_comp_stride(chunk_bytes));
     w.bytes = k.bytes();
     return w;
 }
-
-u32 groups_of(u64 n) { return static_cast<u32>((n + 255) / 256); }
 
 }  // namespace
 
@@ -396,20 +350,16 @@ snp_status snp_frame_append_indexed_batch(snp_ctx* c, uint8_t* buf, const uint64
         if (ok) {
             hipLaunchKernelGGL(k_fa_fail, dim3(tg), dim3(256), 0, s, T, w.rows, w.tl, w.st);
             hipLaunchKernelGGL(k_fa_overlay, dim3(std::min(T, kOverlayGroups)), dim3(256), 0, s, a, w.st, T, w.tl, w.raw);
-            ok = c->check(hipGetLastError(), "frame append overlay") &&
-                 c->launch_compress(w.raw, w.tl.in_off, w.tl.len, T, w.comp, w.tl.coff, w.tl.comp_len, w.tl.c_status, 1) &&
-                 c->check(snp_launch_crc32c(w.raw, w.tl.in_off, w.tl.len, T, 1 | c->crc_bits(), w.tl.crc, nullptr, nullptr, s), "frame append tail crc");
+            ok = c->check(hipGetLastError(), "frame append overlay") && compress_slots(c, w.raw, w.tl.rw(), T, w.comp, "frame append tail");
         }
     }
     if (ok && M) {
-        // the fresh chunks straight from src: no copy of the appended bytes
         hipLaunchKernelGGL(k_fa_fresh, dim3(mg), dim3(256), 0, s, a, w.st, admit, w.fr, stride);
-        ok = c->check(hipGetLastError(), "frame append fresh") &&
-             c->launch_compress(src, w.fr.in_off, w.fr.len, M, w.comp, w.fr.coff, w.fr.comp_len, w.fr.c_status, 1) &&
-             c->check(snp_launch_crc32c(src, w.fr.in_off, w.fr.len, M, 1 | c->crc_bits(), w.fr.crc, nullptr, nullptr, s), "frame append crc");
+        ok = c->check(hipGetLastError(), "frame append fresh");
     }
-    // the framed sizes of the fresh chunks, every stream's verdict, the rows of the new index
-    ok = ok && c->check(launch_scan(ScanFramed{w.fr.len, w.fr.comp_len}, M, w.part, w.cscan, nullptr, s), "frame append size scan");
+    // the fresh chunks re-encoded straight from src (no copy of the appended bytes) and their framed sizes; every stream's verdict, the rows of the
+    // new index
+    ok = ok && reencode_slots(c, src, w.fr.rw(), M, w.comp, w.part, w.cscan, "frame append");
     if (ok) {
         hipLaunchKernelGGL(k_fa_sizes, dim3(sg), dim3(256), 0, s, a, w.st, admit, w.tl, w.cscan, new_len, status, out_bound, d_result);
         ok = c->check(hipGetLastError(), "frame append sizes") &&

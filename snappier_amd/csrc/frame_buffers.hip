@@ -116,11 +116,7 @@ __global__ __launch_bounds__(256) void k_fe_emit(const u32* __restrict__ c_owner
     bool shrink;
     const u32 pl = payload_of(comp_len[c], c_in_len[c], &shrink);
     u8* const dst = out + out_off[b] + SNP_STREAM_HEADER_LEN + (cscan[c] - cscan[first[b]]);
-    if (tid < SNP_CHUNK_HEADER_LEN) {
-        const u32 bs = pl + 4;                                          // :236,251
-        const u32 v = tid == 0 ? (shrink ? 0u : 1u) : tid < 4 ? (bs >> (8 * (tid - 1))) : (crc[c] >> (8 * (tid - 4)));
-        dst[tid] = static_cast<u8>(v);
-    }
+    chunk_header(dst, tid, shrink ? 0u : 1u, pl, crc[c]);
     const u8* const src = shrink ? stage + static_cast<u64>(c) * kSnpCompStride : in + c_in_off[c];
     block_copy(dst + SNP_CHUNK_HEADER_LEN, src, pl, tid);
 }

@@ -124,11 +124,7 @@ __global__ __launch_bounds__(256) void k_fc_emit(u32 max_chunks, u32 group, u32 
         const u32 pl = payload_of(comp_len[c], c_in_len[c], &shrink);
         const u64 pos = SNP_STREAM_HEADER_LEN + (cscan[c] - cscan[first[b]]);
         u8* const dst = out + out_off[b] + pos;
-        if (t < SNP_CHUNK_HEADER_LEN) {
-            const u32 bs = pl + 4;                                      // :236,251
-            const u32 v = t == 0 ? (shrink ? 0u : 1u) : t < 4 ? (bs >> (8 * (t - 1))) : (crc[c] >> (8 * (t - 4)));
-            dst[t] = static_cast<u8>(v);
-        }
+        chunk_header(dst, t, shrink ? 0u : 1u, pl, crc[c]);
         if (idx_start && t == 0) {
             const FcRow r = fc_row(ok_first[b], c - first[b], cb);
             idx_start[r.row] = r.start;

@@ -3,8 +3,8 @@
 // slot's compressed bytes are staged, how many slots one emit workgroup takes, and the index row of a chunk once the scan over the OK buffers'
 // chunk counts exists.  __host__ __device__ throughout, so that the same code runs on the CPU under sanitizers
 // (tests/abi/frame_chunked_plan_check.hip) on buffers past 4 GiB, where k * chunk_bytes does not fit 32 bits.  DESIGN.md 4.15.
-// At the end, device only: what the emit kernel of this call shares with that of the append (frame_append.hip) -- the stream identifier, the
-// CompressBlock rule for a chunk's payload, and team_copy.
+// At the end, device only: what the emit kernel of this call shares with those of the five calls that rewrite seekable streams (through
+// frame_rewrite_device.h) -- the stream identifier, the CompressBlock rule for a chunk's payload, and team_copy.
 //
 // first[0 .. nb] is the exclusive scan of fc_chunks(in_len[b], cb) (first[nb] = the slots the batch needs); ok_first[0 .. nb] the same scan over
 // the buffers whose status is SNP_OK only, made after the size verdict: an out_cap failure can hit a buffer in the middle of the batch, so the
@@ -64,7 +64,7 @@ __host__ __device__ __forceinline__ u64 fc_stage_off(u32 c, u64 stride) { return
 struct FcRow { u64 row, start; };
 __host__ __device__ __forceinline__ FcRow fc_row(u64 ok_first_b, u64 k, u32 cb) { return FcRow{ok_first_b + k, k * cb}; }
 
-// ---- what the emit kernels of the chunked encode and of the append (frame_append.hip) share -------------------------------------------------------
+// ---- what the emit kernels of the chunked encode and of the rewrite calls (frame_rewrite_device.h) share ---------------------------------------
 __constant__ u8 k_fc_stream_id[SNP_STREAM_HEADER_LEN] = {0xff, 0x06, 0x00, 0x00, 0x73, 0x4e, 0x61, 0x50, 0x70, 0x59};   // SnappyStreamCompressor.cs:18-21
 
 __device__ __forceinline__ u32 payload_of(u32 comp, u32 raw, bool* shrink)

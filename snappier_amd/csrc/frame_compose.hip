@@ -1,8 +1,9 @@
 // frame_compose.hip -- snp_frame_compose_indexed_batch: NEW framed streams made of windows ("segments") of old ones that are kept with their
 // chunk index, out of place, with the new index.  A chunk that lies inside a segment is copied untouched; only the chunk a segment cuts at its
 // head and the one it cuts at its tail are decoded, and the parts inside the segment compressed again, with no read-back between the two.
-// frame_compose_device.h plans a segment and maps the rows of an output, frame_chunked_device.h gives the emit its shape.  Built into
-// libsnappier_hip_frame_compose.so (C-ABI: include/snappier_hip_frame_compose.h), linked against libsnappier_hip.so.  DESIGN.md 4.21.
+// frame_compose_device.h plans a segment and maps the rows of an output; the slot table, its re-encode, the piece table and the emit are
+// frame_rewrite_device.h's, shared with the rechunk call.  Built into libsnappier_hip_frame_compose.so (C-ABI:
+// include/snappier_hip_frame_compose.h), linked against libsnappier_hip.so.  DESIGN.md 4.21, 4.17.
 //
 //   plan      a workgroup per segment: cc_begin (the index alone), its rows walked by the threads (cc_add; joined over the workgroup), thread 0:
 //             cc_finish -- the verdict, the edges, the pieces, the kept rows, what it asks of every bound
@@ -14,20 +15,19 @@
 //             the output's staging bytes + the edges before it
 //   decode    snp_ctx::decode_chunks over the table into staging; fail: one thread per row, a failing row -> its output (the first in order)
 //   slots     one thread per table slot: its output, its segment (over the piece scan), cc_piece -> where the piece lies in staging
-//   compress  snp_ctx::launch_compress and snp_launch_crc32c over every slot -- once each, from staging
-//   scan      8 + payload per slot
+//   re-encode reencode_slots: snp_ctx::launch_compress and snp_launch_crc32c over every slot -- once each, from staging; the scan of 8 + payload
+//             per slot
 //   sizes     one thread per output: size against out_cap, status, out_len, out_bound, d_result[0], [1], [3], [5]; its emit units; its new rows;
 //             the identifier of an output without chunks
 //   scans     emit units, rows of the new index
 //   rows      one thread per new row: its output, its segment (over the row scan), cc_row -- an old row (its chunk's place in `in` and size)
 //             or a piece (its slot and framed size); per output: new_first, new_total, new_tail
 //   scan      the chunk sizes of the new rows -> where each chunk lies
-//   emit      one 256-thread workgroup per unit, grid-stride: fc_group(chunk_bytes) consecutive new chunks of a written output, a team each
-//             (k_fc_emit's shape): a kept chunk copied from `in`, or header + payload from staging; new_pos of the row
+//   emit      k_rw_emit: one 256-thread workgroup per unit, grid-stride: fc_group(chunk_bytes) consecutive new chunks of a written output, a
+//             team each: a kept chunk copied from `in`, or header + payload from staging; new_pos of the row
 // Nothing here allocates, reads back or synchronises: the call is capturable like the other _batch entry points.
 #include "capi_internal.h"
-#include "scan_tiles.h"
-#include "work_carver.h"
+#include "frame_rewrite_device.h"
 #include "frame_compose_device.h"
 #include "../../include/snappier_hip_frame_compose.h"
 
@@ -35,10 +35,6 @@ namespace {
 
 constexpr u32 kPass = 0x100u, kWritten = 0x200u;                    // output flags above the status byte
 constexpr u32 kHead = 0x100u, kTail = 0x200u;                       // segment flags above the status byte
-constexpr u64 kNoFail = ~0ull;
-constexpr u64 kRebuilt = 1ull << 63;                                // a new row's source: a slot, not a place in `in`
-constexpr u32 kEmitGroups = 2048;                                   // grid of the grid-stride emit: 8 workgroups per CU
-constexpr u32 kRowGroups = 1u << 20;                                // ... of the new rows
 
 struct CpArgs {
     const u8* in;
@@ -65,38 +61,6 @@ struct CpOuts {
     u64 *nrows, *units;                                     // rows of its new index; emit units
     u64 *aedge, *aslots, *abytes, *arows, *nfirst, *gfirst; // scans (nout + 1): of the four counts; new rows; emit units
     u32* flags;
-};
-// per table slot: what the compressor, the CRC and the emit read
-struct CpSlots {
-    u64 *in_off, *coff;
-    u32 *len, *comp_len, *crc;
-    i32* c_status;
-};
-// per new row
-struct CpPieces {
-    u64* src;                                               // kept: the old chunk's header, in `in`; kRebuilt | slot
-    u32* size;                                              // the chunk's bytes in the new stream
-    u64* scan;                                              // (max_entries + 1)
-};
-
-struct ScanWords {
-    const u64* __restrict__ src;
-    __device__ __forceinline__ u64 operator()(u64 i) const { return src[i]; }
-};
-struct ScanFramed {
-    const u32* __restrict__ len;
-    const u32* __restrict__ comp_len;
-    __device__ __forceinline__ u64 operator()(u64 i) const
-    {
-        bool shrink;
-        return len[i] ? SNP_CHUNK_HEADER_LEN + payload_of(comp_len[i], len[i], &shrink) : 0;
-    }
-};
-struct ScanPieces {
-    const u32* __restrict__ size;
-    const u64* __restrict__ nrows;                          // nfirst + nout: the rows there are
-    u64 cap;
-    __device__ __forceinline__ u64 operator()(u64 i) const { return i < (*nrows < cap ? *nrows : cap) ? size[i] : 0; }
 };
 
 // admission in output order: all four sums only grow
@@ -237,13 +201,13 @@ __global__ __launch_bounds__(256) void k_cc_fail(u32 nout, u32 max_slots, ChunkR
 {
     const u32 t = blockIdx.x * 256u + threadIdx.x;
     if (t >= max_slots || rows.tag[t] == kNone) return;
-    const i32 s = rows.status[t] != SNP_OK ? rows.status[t] : rows.out_len[t] != rows.out_cap[t] ? SNP_ERR_INCOMPLETE : SNP_OK;
+    const i32 s = row_verdict(rows, t);
     if (s != SNP_OK) atomic_min64(o.fail + fc_owner(o.aedge, nout, t), (static_cast<u64>(t) << 8) | static_cast<u64>(s & 0xff));
 }
 
 // One thread per table slot: piece m of an admitted output is slot aslots[j] + m, the pieces in segment order, head before tail; its bytes lie
 // in what its edge decoded to -- there is no assemble pass.
-__global__ __launch_bounds__(256) void k_cc_slots(CpArgs a, CpSegs sg, CpOuts o, Admit admit, CpSlots sl, u64 stride)
+__global__ __launch_bounds__(256) void k_cc_slots(CpArgs a, CpSegs sg, CpOuts o, Admit admit, RwSlots sl, u64 stride)
 {
     const u32 c = blockIdx.x * 256u + threadIdx.x;
     if (c >= admit.max_slots) return;
@@ -309,22 +273,13 @@ __global__ __launch_bounds__(256) void k_cc_sizes(CpArgs a, CpOuts o, Admit admi
         o.nrows[j] = rows;
         o.units[j] = units;
     }
-    ok_len = wave_sum(ok_len);
-    ok = wave_sum(ok);
-    copied = wave_sum(copied);
-    if ((threadIdx.x & 63u) == 0) {
-        if (ok) {
-            atomic_add64(result + 1, ok_len);
-            atomic_add64(result + 3, ok);
-        }
-        if (copied) atomic_add64(result + 5, copied);
-    }
+    add_written(result, ok_len, ok, copied);
 }
 
 // One thread per row of the new index, grid-stride, and per output its three words.  Row i of output j = owner(nfirst, i) is row q of segment
 // g = the owner of i - nfirst[j] among the output's segments; cc_row says what it is.  Only written outputs have rows, and they were admitted
 // with them.
-__global__ __launch_bounds__(256) void k_cc_rows(CpArgs a, CpSegs sg, CpOuts o, const u64* __restrict__ cscan, CpPieces pc, u64 cap,
+__global__ __launch_bounds__(256) void k_cc_rows(CpArgs a, CpSegs sg, CpOuts o, const u64* __restrict__ cscan, RwPieces pc, u64 cap,
                                                 const i32* __restrict__ status, u64* __restrict__ new_first, u64* __restrict__ new_start,
                                                 u64* __restrict__ new_pos, u64* __restrict__ new_total, i32* __restrict__ new_tail)
 {
@@ -368,54 +323,12 @@ __global__ __launch_bounds__(256) void k_cc_rows(CpArgs a, CpSegs sg, CpOuts o, 
     }
 }
 
-// [type:1][len:3 LE = payload + 4][masked crc:4 LE] of a chunk, by the first 8 threads of a team
-__device__ __forceinline__ void chunk_header(u8* at, u32 t, bool shrink, u32 pl, u32 crc)
-{
-    if (t < SNP_CHUNK_HEADER_LEN) {
-        const u32 bs = pl + 4;                                          // SnappyStreamCompressor.cs:236,251
-        const u32 v = t == 0 ? (shrink ? 0u : 1u) : t < 4 ? (bs >> (8 * (t - 1))) : (crc >> (8 * (t - 4)));
-        at[t] = static_cast<u8>(v);
-    }
-}
-
-// One workgroup per emit unit of a written output: `group` consecutive chunks of the new stream, taken by teams of `team` threads in turn
-// (k_fc_emit's shape).  A kept chunk is copied from its source as it is; a piece is its header and what the compressor or the staging holds.
-// The unit steers the whole workgroup, a chunk its whole team.  The first unit of an output writes the identifier.
-__global__ __launch_bounds__(256) void k_cc_emit(CpArgs a, CpOuts o, CpSlots sl, CpPieces pc, u32 group, u32 team, const u8* __restrict__ stage,
-                                                const u8* __restrict__ comp, u8* __restrict__ out, const u64* __restrict__ out_off,
-                                                u64* __restrict__ new_pos)
-{
-    const u32 tid = threadIdx.x, t = tid % team, teams = 256u / team;
-    const u64 units = o.gfirst[a.nout];
-    for (u64 u0 = blockIdx.x; u0 < units; u0 += gridDim.x) {
-        const u32 j = fc_owner(o.gfirst, a.nout, u0);
-        const u64 u = u0 - o.gfirst[j], first = o.nfirst[j], last = o.nfirst[j + 1];
-        const u64 i0 = first + u * group, i1 = i0 + group < last ? i0 + group : last;
-        u8* const dst = out + out_off[j];
-        if (u == 0 && tid < SNP_STREAM_HEADER_LEN) dst[tid] = k_fc_stream_id[tid];       // EnsureStreamHeaderWritten  SnappyStreamCompressor.cs:148-157
-        for (u64 i = i0 + tid / team; i < i1; i += teams) {
-            const u64 src = pc.src[i], pos = SNP_STREAM_HEADER_LEN + (pc.scan[i] - pc.scan[first]);
-            if (t == 0) new_pos[i] = pos;
-            if (pc.size[i] == 0) continue;
-            if (!(src & kRebuilt)) {
-                team_copy(dst + pos, a.in + src, pc.size[i], t, team);
-                continue;
-            }
-            const u64 c = src & ~kRebuilt;
-            bool shrink;
-            const u32 pl = payload_of(sl.comp_len[c], sl.len[c], &shrink);
-            chunk_header(dst + pos, t, shrink, pl, sl.crc[c]);
-            team_copy(dst + pos + SNP_CHUNK_HEADER_LEN, shrink ? comp + sl.coff[c] : stage + sl.in_off[c], pl, t, team);
-        }
-    }
-}
-
 // workspace (every piece 256-byte aligned; nothing when there is no output)
 struct ComposeWork {
     CpSegs sg;
     CpOuts o;
-    CpSlots sl;
-    CpPieces pc;
+    RwSlots sl;
+    RwPieces pc;
     ChunkRows rows;
     u64 *part, *cscan;
     u8 *stage, *comp;
@@ -436,26 +349,17 @@ ComposeWork work_layout(void* base, u32 nout, u32 nsegs, u32 max_slots, u64 stag
     for (u64** p : {&w.o.cedge, &w.o.cslots, &w.o.cstage, &w.o.crows, &w.o.kbytes, &w.o.bound, &w.o.fail, &w.o.nrows, &w.o.units}) *p = k.take<u64>(no);
     for (u64** p : {&w.o.aedge, &w.o.aslots, &w.o.abytes, &w.o.arows, &w.o.nfirst, &w.o.gfirst}) *p = k.take<u64>(no + 1);
     w.o.flags = k.take<u32>(no);
-    w.sl.in_off = k.take<u64>(M);
-    w.sl.coff = k.take<u64>(M);
-    w.sl.len = k.take<u32>(M);
-    w.sl.comp_len = k.take<u32>(M);
-    w.sl.crc = k.take<u32>(M);
-    w.sl.c_status = k.take<i32>(M);
+    w.sl = carve_rw_slots(k, M);
     w.rows = carve_chunk_rows(k, M);
     w.cscan = k.take<u64>(M + 1);
-    w.pc.src = k.take<u64>(E);
-    w.pc.size = k.take<u32>(E);
-    w.pc.scan = k.take<u64>(E + 1);
+    w.pc = carve_rw_pieces(k, E);
     // staging: per admitted output what its edges decode to, one behind the other, the outputs back to back (+ slack for the compressor's
-    // vector loads).  Compressed staging: slot c at c * snp_comp_stride(chunk_bytes), as in frame_chunked.hip.
+    // vector loads).  Compressed staging: slot c at c * snp_comp_stride(chunk_bytes) (fc_stage_off).
     w.stage = k.take<u8>(stage_cap + 256);
     w.comp = k.take<u8>(M * snp_comp_stride(chunk_bytes));
     w.bytes = k.bytes();
     return w;
 }
-
-u32 groups_of(u64 n) { return static_cast<u32>((n + 255) / 256); }
 
 }  // namespace
 
@@ -516,16 +420,14 @@ snp_status snp_frame_compose_indexed_batch(snp_ctx* c, const uint8_t* in, const 
         hipLaunchKernelGGL(k_cc_fill, dim3(mg), dim3(256), 0, s, a, w.sg, w.o, admit, w.rows);
         ok = c->check(hipGetLastError(), "frame compose fill") && c->decode_chunks(in, w.rows, M, w.stage);
         if (ok) {
-            // CompressBlock of every piece and its masked CRC-32C: one launch each, from where the edges were decoded to
             hipLaunchKernelGGL(k_cc_fail, dim3(mg), dim3(256), 0, s, no, M, w.rows, w.o);
             hipLaunchKernelGGL(k_cc_slots, dim3(mg), dim3(256), 0, s, a, w.sg, w.o, admit, w.sl, snp_comp_stride(cb));
-            ok = c->check(hipGetLastError(), "frame compose slots") &&
-                 c->launch_compress(w.stage, w.sl.in_off, w.sl.len, M, w.comp, w.sl.coff, w.sl.comp_len, w.sl.c_status, 1) &&
-                 c->check(snp_launch_crc32c(w.stage, w.sl.in_off, w.sl.len, M, 1 | c->crc_bits(), w.sl.crc, nullptr, nullptr, s), "frame compose crc");
+            ok = c->check(hipGetLastError(), "frame compose slots");
         }
     }
-    // the framed sizes of the pieces, every output's verdict, its emit units and the rows of its new index
-    ok = ok && c->check(launch_scan(ScanFramed{w.sl.len, w.sl.comp_len}, M, w.part, w.cscan, nullptr, s), "frame compose size scan");
+    // every piece re-encoded from where the edges were decoded to, and the framed sizes; every output's verdict, its emit units and the rows of
+    // its new index
+    ok = ok && reencode_slots(c, w.stage, w.sl, M, w.comp, w.part, w.cscan, "frame compose");
     if (ok) {
         const u32 group = fc_group(cb);
         hipLaunchKernelGGL(k_cc_sizes, dim3(og), dim3(256), 0, s, a, w.o, admit, w.cscan, group, out, out_off, out_cap, out_len, status, out_bound,
@@ -540,8 +442,8 @@ snp_status snp_frame_compose_indexed_batch(snp_ctx* c, const uint8_t* in, const 
             ok = c->check(hipGetLastError(), "frame compose rows") &&
                  c->check(launch_scan(ScanPieces{w.pc.size, w.o.nfirst + no, E}, E, w.part, w.pc.scan, nullptr, s), "frame compose chunk scan");
             if (ok) {
-                hipLaunchKernelGGL(k_cc_emit, dim3(kEmitGroups), dim3(256), 0, s, a, w.o, w.sl, w.pc, group, fc_team(group), w.stage, w.comp, out, out_off,
-                                   new_pos);
+                hipLaunchKernelGGL(k_rw_emit<RwOwners>, dim3(kEmitGroups), dim3(256), 0, s, RwOwners{w.o.gfirst, w.o.nfirst, no}, w.sl, w.pc, group, fc_team(group),
+                                   in, w.stage, w.comp, out, out_off, new_pos);
                 ok = c->check(hipGetLastError(), "frame compose emit");
             }
         }

@@ -1,8 +1,9 @@
 // frame_rechunk.hip -- snp_frame_rechunk_indexed_batch: framed streams kept with their chunk index brought to CANONICAL form -- what
 // snp_frame_encode_chunked_batch writes for their decoded bytes with chunk_bytes -- out of place, with the new index.  An old chunk that already
 // is a piece of the new stream is copied; only the other pieces are decoded and compressed again, with no read-back between the two.
-// frame_rechunk_device.h plans a stream, frame_chunked_device.h gives the emit its shape.  Built into libsnappier_hip_frame_rechunk.so (C-ABI:
-// include/snappier_hip_frame_rechunk.h), linked against libsnappier_hip.so.  DESIGN.md 4.20.
+// frame_rechunk_device.h plans a stream; the slot table, its re-encode, the piece table and the emit are frame_rewrite_device.h's, shared with
+// the compose call.  Built into libsnappier_hip_frame_rechunk.so (C-ABI: include/snappier_hip_frame_rechunk.h), linked against
+// libsnappier_hip.so.  DESIGN.md 4.20, 4.17.  The kernels here are k_rc_*: k_fr_* are frame_range.hip's.
 //
 //   plan      a workgroup per stream walks its rows (fr_row, fr_add; joined over the workgroup): the partition, every header, clean or dirty;
 //             thread 0: fr_finish -- the verdict so far, canonical or not, the dirty rows, the rebuilt pieces, the staging bytes, the size bound
@@ -12,29 +13,24 @@
 //             bytes + the decoded bytes of the dirty rows before it
 //   decode    snp_ctx::decode_chunks over the table into staging; fail: one thread per row, a failing row -> its stream (the first in order)
 //   slots     one thread per table slot (fc_owner): the m-th rebuilt piece of its stream lies at m * chunk_bytes of the stream's staging bytes
-//   compress  snp_ctx::launch_compress and snp_launch_crc32c over every slot -- once each, from staging
-//   scan      8 + payload per slot
+//   re-encode reencode_slots: snp_ctx::launch_compress and snp_launch_crc32c over every slot -- once each, from staging; the scan of 8 + payload
+//             per slot
 //   sizes     one thread per stream: size against out_cap, status, out_len, out_bound, d_result[0], [1], [3], [5]; its emit units; its new rows
 //   scans     emit units, rows of the new index
-//   rows      one thread per new row: an old row copied, or piece k of a written stream -- kept (the old chunk's place and size) or rebuilt (its
-//             slot and framed size); per stream: new_first, new_total, new_tail
+//   rows      one thread per new row: an old row copied, or piece k of a written stream -- kept (the old chunk's place in `in` and size) or
+//             rebuilt (its slot and framed size); per stream: new_first, new_total, new_tail
 //   scan      the chunk sizes of the new rows -> where each chunk lies
-//   emit      one 256-thread workgroup per unit, grid-stride: fc_group(chunk_bytes) consecutive new chunks of a written stream, a team each
-//             (k_fc_emit's shape): a kept chunk copied from `in`, or header + payload from staging; new_pos of the row
+//   emit      k_rw_emit: one 256-thread workgroup per unit, grid-stride: fc_group(chunk_bytes) consecutive new chunks of a written stream, a
+//             team each: a kept chunk copied from `in`, or header + payload from staging; new_pos of the row
 // Nothing here allocates, reads back or synchronises: the call is capturable like the other _batch entry points.
 #include "capi_internal.h"
-#include "scan_tiles.h"
-#include "work_carver.h"
+#include "frame_rewrite_device.h"
 #include "frame_rechunk_device.h"
 #include "../../include/snappier_hip_frame_rechunk.h"
 
 namespace {
 
 constexpr u32 kWork = 0x100u, kLast = 0x200u, kWritten = 0x400u;    // stream flags above the status byte
-constexpr u64 kNoFail = ~0ull;
-constexpr u64 kRebuilt = 1ull << 63;                                // a new row's source: a slot, not a place in the old stream
-constexpr u32 kEmitGroups = 2048;                                   // grid of the grid-stride emit: 8 workgroups per CU
-constexpr u32 kRowGroups = 1u << 20;                                // ... of the new rows
 
 struct RcArgs {
     const u8* in;
@@ -52,38 +48,6 @@ struct RcStreams {
     u64 *nrows, *units;                                     // rows of its new index; emit units
     u64 *adirty, *aslots, *abytes, *arows, *nfirst, *gfirst;// scans (n + 1): of the four counts; new rows; emit units
     u32* flags;
-};
-// per table slot: what the compressor, the CRC and the emit read
-struct RcSlots {
-    u64 *in_off, *coff;
-    u32 *len, *comp_len, *crc;
-    i32* c_status;
-};
-// per new row
-struct RcPieces {
-    u64* src;                                               // kept: the old chunk's header, stream-relative; kRebuilt | slot
-    u32* size;                                              // the chunk's bytes in the new stream (0: a row of a stream that is not written)
-    u64* scan;                                              // (max_entries + 1)
-};
-
-struct ScanWords {
-    const u64* __restrict__ src;
-    __device__ __forceinline__ u64 operator()(u64 i) const { return src[i]; }
-};
-struct ScanFramed {
-    const u32* __restrict__ len;
-    const u32* __restrict__ comp_len;
-    __device__ __forceinline__ u64 operator()(u64 i) const
-    {
-        bool shrink;
-        return len[i] ? SNP_CHUNK_HEADER_LEN + payload_of(comp_len[i], len[i], &shrink) : 0;
-    }
-};
-struct ScanPieces {
-    const u32* __restrict__ size;
-    const u64* __restrict__ nrows;                          // nfirst + ns: the rows there are
-    u64 cap;
-    __device__ __forceinline__ u64 operator()(u64 i) const { return i < (*nrows < cap ? *nrows : cap) ? size[i] : 0; }
 };
 
 // admission in stream order: all four sums only grow
@@ -131,7 +95,7 @@ __device__ __forceinline__ FrAcc block_join(FrAcc a, u64* s)
 }
 
 // A workgroup per stream.  The stream steers the whole workgroup.
-__global__ __launch_bounds__(256) void k_fr_plan(RcArgs a, RcStreams st)
+__global__ __launch_bounds__(256) void k_rc_plan(RcArgs a, RcStreams st)
 {
     __shared__ u64 s_acc[8];
     const u32 b = blockIdx.x;
@@ -164,7 +128,7 @@ __global__ __launch_bounds__(256) void k_fr_plan(RcArgs a, RcStreams st)
 }
 
 // One thread per row of the decode table: an empty row.
-__global__ __launch_bounds__(256) void k_fr_clear(u32 max_slots, ChunkRows rows, u64* __restrict__ dstart)
+__global__ __launch_bounds__(256) void k_rc_clear(u32 max_slots, ChunkRows rows, u64* __restrict__ dstart)
 {
     const u32 t = blockIdx.x * 256u + threadIdx.x;
     if (t >= max_slots) return;
@@ -188,7 +152,7 @@ __device__ __forceinline__ u64 wave_scan(u64 v, u64* total)
 
 // A workgroup per admitted stream walks its rows again, 256 at a time, with the dirty rows and their decoded bytes so far: dirty row j of the
 // stream is row adirty[b] + j of the table and decodes to the stream's staging bytes + the decoded bytes of the dirty rows before it.
-__global__ __launch_bounds__(256) void k_fr_fill(RcArgs a, RcStreams st, Admit admit, ChunkRows rows, u64* __restrict__ dstart)
+__global__ __launch_bounds__(256) void k_rc_fill(RcArgs a, RcStreams st, Admit admit, ChunkRows rows, u64* __restrict__ dstart)
 {
     __shared__ u64 s_cnt[4], s_byt[4];
     const u32 b = blockIdx.x;
@@ -226,16 +190,16 @@ __global__ __launch_bounds__(256) void k_fr_fill(RcArgs a, RcStreams st, Admit a
 }
 
 // a dirty row that did not decode or verify: its status to its stream, the first row's in stream order
-__global__ __launch_bounds__(256) void k_fr_fail(u32 ns, u32 max_slots, ChunkRows rows, RcStreams st)
+__global__ __launch_bounds__(256) void k_rc_fail(u32 ns, u32 max_slots, ChunkRows rows, RcStreams st)
 {
     const u32 t = blockIdx.x * 256u + threadIdx.x;
     if (t >= max_slots || rows.tag[t] == kNone) return;
-    const i32 s = rows.status[t] != SNP_OK ? rows.status[t] : rows.out_len[t] != rows.out_cap[t] ? SNP_ERR_INCOMPLETE : SNP_OK;
+    const i32 s = row_verdict(rows, t);
     if (s != SNP_OK) atomic_min64(st.fail + owner_of(static_cast<const u64*>(st.adirty), ns, t), (static_cast<u64>(t) << 8) | static_cast<u64>(s & 0xff));
 }
 
 // One thread per table slot: the m-th rebuilt piece of its stream in staging and where its compressed bytes are staged.
-__global__ __launch_bounds__(256) void k_fr_slots(RcArgs a, RcStreams st, Admit admit, RcSlots sl, u64 stride)
+__global__ __launch_bounds__(256) void k_rc_slots(RcArgs a, RcStreams st, Admit admit, RwSlots sl, u64 stride)
 {
     const u32 c = blockIdx.x * 256u + threadIdx.x;
     if (c >= admit.max_slots) return;
@@ -258,7 +222,7 @@ __global__ __launch_bounds__(256) void k_fr_slots(RcArgs a, RcStreams st, Admit 
     sl.len[c] = len;
 }
 
-__global__ __launch_bounds__(256) void k_fr_sizes(RcArgs a, RcStreams st, Admit admit, const u64* __restrict__ cscan, u32 group,
+__global__ __launch_bounds__(256) void k_rc_sizes(RcArgs a, RcStreams st, Admit admit, const u64* __restrict__ cscan, u32 group,
                                                  const u64* __restrict__ out_cap, u64* __restrict__ out_len, i32* __restrict__ status,
                                                  u64* __restrict__ out_bound, u64* __restrict__ result)
 {
@@ -297,24 +261,15 @@ __global__ __launch_bounds__(256) void k_fr_sizes(RcArgs a, RcStreams st, Admit 
         st.nrows[b] = rows;
         st.units[b] = units;
     }
-    ok_len = wave_sum(ok_len);
-    ok = wave_sum(ok);
-    alone = wave_sum(alone);
-    if ((threadIdx.x & 63u) == 0) {
-        if (ok) {
-            atomic_add64(result + 1, ok_len);
-            atomic_add64(result + 3, ok);
-        }
-        if (alone) atomic_add64(result + 5, alone);
-    }
+    add_written(result, ok_len, ok, alone);
 }
 
 // One thread per row of the new index, grid-stride, and per stream its three words.  Row i of stream b = owner(nfirst, i): of a stream that is
 // not written, one of its old rows (f0 and the count are clamped to nentries: idx_first is untrusted); of a written one, piece i - nfirst[b]:
 // kept -- the old chunk, its size from its header -- or rebuilt -- the slot of the dirty row that holds its first byte.  Rows at or past `cap` do
 // not exist (a written stream's all do: it was admitted with them).
-__global__ __launch_bounds__(256) void k_fr_rows(RcArgs a, RcStreams st, Admit admit, ChunkRows rows, const u64* __restrict__ dstart,
-                                                const u64* __restrict__ cscan, RcPieces pc, u64 cap, u64* __restrict__ new_first,
+__global__ __launch_bounds__(256) void k_rc_rows(RcArgs a, RcStreams st, Admit admit, ChunkRows rows, const u64* __restrict__ dstart,
+                                                const u64* __restrict__ cscan, RwPieces pc, u64 cap, u64* __restrict__ new_first,
                                                 u64* __restrict__ new_start, u64* __restrict__ new_pos, u64* __restrict__ new_total,
                                                 i32* __restrict__ new_tail)
 {
@@ -356,59 +311,16 @@ __global__ __launch_bounds__(256) void k_fr_rows(RcArgs a, RcStreams st, Admit a
             }
         }
         new_start[i] = p.at;
-        pc.src[i] = src;
+        pc.src[i] = p.kept ? a.in_off[b] + src : src;                   // a kept chunk by its place in `in` (added here: 21 VGPRs, not 25)
         pc.size[i] = size;
-    }
-}
-
-// [type:1][len:3 LE = payload + 4][masked crc:4 LE] of a chunk, by the first 8 threads of a team
-__device__ __forceinline__ void chunk_header(u8* at, u32 t, bool shrink, u32 pl, u32 crc)
-{
-    if (t < SNP_CHUNK_HEADER_LEN) {
-        const u32 bs = pl + 4;                                          // SnappyStreamCompressor.cs:236,251
-        const u32 v = t == 0 ? (shrink ? 0u : 1u) : t < 4 ? (bs >> (8 * (t - 1))) : (crc >> (8 * (t - 4)));
-        at[t] = static_cast<u8>(v);
-    }
-}
-
-// One workgroup per emit unit of a written stream: `group` consecutive chunks of the new stream, taken by teams of `team` threads in turn
-// (k_fc_emit's shape).  A kept chunk is copied from the old stream as it is; a rebuilt one is its header and what the compressor or the staging
-// holds.  The unit steers the whole workgroup, a chunk its whole team.  The first unit of a stream writes the identifier.
-__global__ __launch_bounds__(256) void k_fr_emit(RcArgs a, RcStreams st, RcSlots sl, RcPieces pc, u32 group, u32 team, const u8* __restrict__ stage,
-                                                const u8* __restrict__ comp, u8* __restrict__ out, const u64* __restrict__ out_off,
-                                                u64* __restrict__ new_pos)
-{
-    const u32 tid = threadIdx.x, t = tid % team, teams = 256u / team;
-    const u64 units = st.gfirst[a.ns];
-    for (u64 g = blockIdx.x; g < units; g += gridDim.x) {
-        const u32 b = owner_of(static_cast<const u64*>(st.gfirst), a.ns, g);
-        const u64 u = g - st.gfirst[b], first = st.nfirst[b], last = st.nfirst[b + 1];
-        const u64 i0 = first + u * group, i1 = i0 + group < last ? i0 + group : last;
-        const u8* const old = a.in + a.in_off[b];
-        u8* const dst = out + out_off[b];
-        if (u == 0 && tid < SNP_STREAM_HEADER_LEN) dst[tid] = k_fc_stream_id[tid];       // EnsureStreamHeaderWritten  SnappyStreamCompressor.cs:148-157
-        for (u64 i = i0 + tid / team; i < i1; i += teams) {
-            const u64 src = pc.src[i], pos = SNP_STREAM_HEADER_LEN + (pc.scan[i] - pc.scan[first]);
-            if (t == 0) new_pos[i] = pos;
-            if (pc.size[i] == 0) continue;
-            if (!(src & kRebuilt)) {
-                team_copy(dst + pos, old + src, pc.size[i], t, team);
-                continue;
-            }
-            const u64 c = src & ~kRebuilt;
-            bool shrink;
-            const u32 pl = payload_of(sl.comp_len[c], sl.len[c], &shrink);
-            chunk_header(dst + pos, t, shrink, pl, sl.crc[c]);
-            team_copy(dst + pos + SNP_CHUNK_HEADER_LEN, shrink ? comp + sl.coff[c] : stage + sl.in_off[c], pl, t, team);
-        }
     }
 }
 
 // workspace (every piece 256-byte aligned; nothing when there is no stream)
 struct RechunkWork {
     RcStreams st;
-    RcSlots sl;
-    RcPieces pc;
+    RwSlots sl;
+    RwPieces pc;
     ChunkRows rows;
     u64 *part, *cscan, *dstart;
     u8 *stage, *comp;
@@ -426,27 +338,18 @@ RechunkWork work_layout(void* base, u32 nstreams, u32 max_slots, u64 stage_cap, 
         *p = k.take<u64>(ns);
     for (u64** p : {&w.st.adirty, &w.st.aslots, &w.st.abytes, &w.st.arows, &w.st.nfirst, &w.st.gfirst}) *p = k.take<u64>(ns + 1);
     w.st.flags = k.take<u32>(ns);
-    w.sl.in_off = k.take<u64>(M);
-    w.sl.coff = k.take<u64>(M);
-    w.sl.len = k.take<u32>(M);
-    w.sl.comp_len = k.take<u32>(M);
-    w.sl.crc = k.take<u32>(M);
-    w.sl.c_status = k.take<i32>(M);
+    w.sl = carve_rw_slots(k, M);
     w.rows = carve_chunk_rows(k, M);
     w.dstart = k.take<u64>(M);
     w.cscan = k.take<u64>(M + 1);
-    w.pc.src = k.take<u64>(E);
-    w.pc.size = k.take<u32>(E);
-    w.pc.scan = k.take<u64>(E + 1);
+    w.pc = carve_rw_pieces(k, E);
     // staging: per admitted stream what its dirty rows decode to, one behind the other, the streams back to back (+ slack for the compressor's
-    // vector loads).  Compressed staging: slot c at c * snp_comp_stride(chunk_bytes), as in frame_chunked.hip.
+    // vector loads).  Compressed staging: slot c at c * snp_comp_stride(chunk_bytes) (fc_stage_off).
     w.stage = k.take<u8>(stage_cap + 256);
     w.comp = k.take<u8>(M * snp_comp_stride(chunk_bytes));
     w.bytes = k.bytes();
     return w;
 }
-
-u32 groups_of(u64 n) { return static_cast<u32>((n + 255) / 256); }
 
 }  // namespace
 
@@ -479,7 +382,7 @@ snp_status snp_frame_rechunk_indexed_batch(snp_ctx* c, const uint8_t* in, const 
     const RcArgs a{in, in_off, in_len, ns, FrameIndex{idx_first, idx_start, idx_pos, idx_total, idx_tail, nentries}, cb, (flags & kFrRewriteAll) != 0};
     const Admit admit{w.st.flags, w.st.adirty, w.st.aslots, w.st.abytes, w.st.arows, M, stage_cap, E};
     // the plan of every stream; admission in stream order (d_result[2] = staging bytes, [4] = new rows; [0] comes with the verdicts)
-    hipLaunchKernelGGL(k_fr_plan, dim3(ns), dim3(256), 0, s, a, w.st);
+    hipLaunchKernelGGL(k_rc_plan, dim3(ns), dim3(256), 0, s, a, w.st);
     ok = ok && c->check(hipGetLastError(), "frame rechunk plan") &&
          c->check(launch_scan(ScanWords{w.st.cdirty}, ns, w.part, w.st.adirty, nullptr, s), "frame rechunk row scan") &&
          c->check(launch_scan(ScanWords{w.st.cslots}, ns, w.part, w.st.aslots, nullptr, s), "frame rechunk slot scan") &&
@@ -487,35 +390,32 @@ snp_status snp_frame_rechunk_indexed_batch(snp_ctx* c, const uint8_t* in, const 
          c->check(launch_scan(ScanWords{w.st.crows}, ns, w.part, w.st.arows, d_result + 4, s), "frame rechunk entry scan");
     if (ok && M) {
         // the dirty rows decoded and verified whole into staging, one behind the other: there the rebuilt pieces lie one behind the other
-        hipLaunchKernelGGL(k_fr_clear, dim3(mg), dim3(256), 0, s, M, w.rows, w.dstart);
-        hipLaunchKernelGGL(k_fr_fill, dim3(ns), dim3(256), 0, s, a, w.st, admit, w.rows, w.dstart);
+        hipLaunchKernelGGL(k_rc_clear, dim3(mg), dim3(256), 0, s, M, w.rows, w.dstart);
+        hipLaunchKernelGGL(k_rc_fill, dim3(ns), dim3(256), 0, s, a, w.st, admit, w.rows, w.dstart);
         ok = c->check(hipGetLastError(), "frame rechunk fill") && c->decode_chunks(in, w.rows, M, w.stage);
         if (ok) {
-            // CompressBlock of every rebuilt piece and its masked CRC-32C: one launch each, from staging
-            hipLaunchKernelGGL(k_fr_fail, dim3(mg), dim3(256), 0, s, ns, M, w.rows, w.st);
-            hipLaunchKernelGGL(k_fr_slots, dim3(mg), dim3(256), 0, s, a, w.st, admit, w.sl, snp_comp_stride(cb));
-            ok = c->check(hipGetLastError(), "frame rechunk slots") &&
-                 c->launch_compress(w.stage, w.sl.in_off, w.sl.len, M, w.comp, w.sl.coff, w.sl.comp_len, w.sl.c_status, 1) &&
-                 c->check(snp_launch_crc32c(w.stage, w.sl.in_off, w.sl.len, M, 1 | c->crc_bits(), w.sl.crc, nullptr, nullptr, s), "frame rechunk crc");
+            hipLaunchKernelGGL(k_rc_fail, dim3(mg), dim3(256), 0, s, ns, M, w.rows, w.st);
+            hipLaunchKernelGGL(k_rc_slots, dim3(mg), dim3(256), 0, s, a, w.st, admit, w.sl, snp_comp_stride(cb));
+            ok = c->check(hipGetLastError(), "frame rechunk slots");
         }
     }
-    // the framed sizes of the rebuilt chunks, every stream's verdict, its emit units and the rows of its new index
-    ok = ok && c->check(launch_scan(ScanFramed{w.sl.len, w.sl.comp_len}, M, w.part, w.cscan, nullptr, s), "frame rechunk size scan");
+    // every rebuilt piece re-encoded from staging and the framed sizes; every stream's verdict, its emit units and the rows of its new index
+    ok = ok && reencode_slots(c, w.stage, w.sl, M, w.comp, w.part, w.cscan, "frame rechunk");
     if (ok) {
         const u32 group = fc_group(cb);
-        hipLaunchKernelGGL(k_fr_sizes, dim3(sg), dim3(256), 0, s, a, w.st, admit, w.cscan, group, out_cap, out_len, status, out_bound, d_result);
+        hipLaunchKernelGGL(k_rc_sizes, dim3(sg), dim3(256), 0, s, a, w.st, admit, w.cscan, group, out_cap, out_len, status, out_bound, d_result);
         ok = c->check(hipGetLastError(), "frame rechunk sizes") &&
              c->check(launch_scan(ScanWords{w.st.units}, ns, w.part, w.st.gfirst, nullptr, s), "frame rechunk unit scan") &&
              c->check(launch_scan(ScanWords{w.st.nrows}, ns, w.part, w.st.nfirst, nullptr, s), "frame rechunk new row scan");
         if (ok) {
             const u64 most = std::max<u64>(E, static_cast<u64>(ns) + 1);
-            hipLaunchKernelGGL(k_fr_rows, dim3(static_cast<u32>(std::min<u64>((most + 255) / 256, kRowGroups))), dim3(256), 0, s, a, w.st, admit, w.rows,
+            hipLaunchKernelGGL(k_rc_rows, dim3(static_cast<u32>(std::min<u64>((most + 255) / 256, kRowGroups))), dim3(256), 0, s, a, w.st, admit, w.rows,
                                w.dstart, w.cscan, w.pc, E, new_first, new_start, new_pos, new_total, new_tail);
             ok = c->check(hipGetLastError(), "frame rechunk rows") &&
                  c->check(launch_scan(ScanPieces{w.pc.size, w.st.nfirst + ns, E}, E, w.part, w.pc.scan, nullptr, s), "frame rechunk chunk scan");
             if (ok) {
-                hipLaunchKernelGGL(k_fr_emit, dim3(kEmitGroups), dim3(256), 0, s, a, w.st, w.sl, w.pc, group, fc_team(group), w.stage, w.comp, out, out_off,
-                                   new_pos);
+                hipLaunchKernelGGL(k_rw_emit<RwOwners>, dim3(kEmitGroups), dim3(256), 0, s, RwOwners{w.st.gfirst, w.st.nfirst, ns}, w.sl, w.pc, group, fc_team(group),
+                                   in, w.stage, w.comp, out, out_off, new_pos);
                 ok = c->check(hipGetLastError(), "frame rechunk emit");
             }
         }

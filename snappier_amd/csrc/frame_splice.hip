@@ -19,18 +19,14 @@
 //   rows      one thread per new row: an old row copied, a new chunk's row from the size scan, or an old row moved; per stream: new_total, new_tail
 // Nothing here allocates, reads back or synchronises: the call is capturable like the other _batch entry points.
 #include "capi_internal.h"
-#include "scan_tiles.h"
-#include "work_carver.h"
+#include "frame_rewrite_device.h"
 #include "frame_splice_device.h"
 #include "../../include/snappier_hip_frame_splice.h"
 
 namespace {
 
 constexpr u32 kSplice = 0x100u, kIdent = 0x200u, kHead = 0x400u, kTail = 0x800u, kWritten = 0x1000u;    // stream flags above the status byte
-constexpr u64 kUnit = 65536;                                        // kept bytes of an old stream one emit workgroup takes at a time
 constexpr u32 kAssemblePieces = 8;                                  // workgroups that share one stream's region
-constexpr u32 kEmitGroups = 2048;                                   // grid of the grid-stride emit: 8 workgroups per CU
-constexpr u32 kRowGroups = 1u << 20;                                // ... of the index merge
 
 struct SpArgs {
     const u8* in;
@@ -50,26 +46,7 @@ struct SpStreams {
     u32 *flags, *hl, *tl, *e0, *e1;
     i32* fail;                                              // the status of an edge that did not decode or verify
 };
-// per table slot: what the compressor, the CRC and the emit read
-struct SpSlots {
-    u64 *in_off, *coff;
-    u32 *len, *stream, *comp_len, *crc;
-    i32* c_status;
-};
-
-struct ScanWords {
-    const u64* __restrict__ src;
-    __device__ __forceinline__ u64 operator()(u64 i) const { return src[i]; }
-};
-struct ScanFramed {
-    const u32* __restrict__ len;
-    const u32* __restrict__ comp_len;
-    __device__ __forceinline__ u64 operator()(u64 i) const
-    {
-        bool shrink;
-        return len[i] ? SNP_CHUNK_HEADER_LEN + payload_of(comp_len[i], len[i], &shrink) : 0;
-    }
-};
+using SpSlots = RwOwnedSlots;                               // per table slot
 
 // admission in stream order: both sums only grow
 struct Admit {
@@ -145,7 +122,7 @@ __global__ __launch_bounds__(256) void k_fs_fail(u32 ns, ChunkRows rows, SpStrea
     i32 s = SNP_OK;
     for (u64 t = 2ull * b; t < 2ull * b + 2 && s == SNP_OK; ++t) {
         if (rows.tag[t] == kNone) continue;
-        s = rows.status[t] != SNP_OK ? rows.status[t] : rows.out_len[t] != rows.out_cap[t] ? SNP_ERR_INCOMPLETE : SNP_OK;
+        s = row_verdict(rows, t);
     }
     st.fail[b] = s;
 }
@@ -245,19 +222,10 @@ __global__ __launch_bounds__(256) void k_fs_sizes(SpArgs a, SpStreams st, Admit 
     }
 }
 
-// [type:1][len:3 LE = payload + 4][masked crc:4 LE] of a chunk, by the first 8 threads of a team
-__device__ __forceinline__ void chunk_header(u8* at, u32 t, bool shrink, u32 pl, u32 crc)
-{
-    if (t < SNP_CHUNK_HEADER_LEN) {
-        const u32 bs = pl + 4;                                          // SnappyStreamCompressor.cs:236,251
-        const u32 v = t == 0 ? (shrink ? 0u : 1u) : t < 4 ? (bs >> (8 * (t - 1))) : (crc >> (8 * (t - 4)));
-        at[t] = static_cast<u8>(v);
-    }
-}
-
 // One workgroup per emit unit of a written stream.  The first units of a stream are 64 KiB each of its KEPT bytes -- the old stream without the hole
 // [P0, P1): a byte before P0 stays where it was, a byte from P1 on moves by new_bytes - (P1 - P0) -- the others are `group` consecutive new chunks
-// each, taken by teams of `team` threads in turn (k_fc_emit's shape).  The unit steers the whole workgroup, a slot its whole team.
+// each, taken by teams of `team` threads in turn (fc_group and fc_team, frame_chunked_device.h; emit_slot, frame_rewrite_device.h).  The unit
+// steers the whole workgroup, a slot its whole team.
 __global__ __launch_bounds__(256) void k_fs_emit(SpArgs a, SpStreams st, SpSlots sl, u32 group, u32 team, const u64* __restrict__ cscan,
                                                 const u8* __restrict__ stage, const u8* __restrict__ comp, u8* __restrict__ out,
                                                 const u64* __restrict__ out_off)
@@ -281,13 +249,9 @@ __global__ __launch_bounds__(256) void k_fs_emit(SpArgs a, SpStreams st, SpSlots
         const u64 c0 = first + (u - kept_units) * group, c1 = c0 + group < last ? c0 + group : last;
         const u64 base = p0 + ((st.flags[b] & kIdent) ? SNP_STREAM_HEADER_LEN : 0);
         for (u64 c = c0 + tid / team; c < c1; c += teams) {
-            const u32 len = sl.len[c];
-            bool shrink;
-            const u32 pl = payload_of(sl.comp_len[c], len, &shrink);
             const u64 pos = base + (cscan[c] - cscan[first]);
             if (c == first && (st.flags[b] & kIdent) && t < SNP_STREAM_HEADER_LEN) dst[t] = k_fc_stream_id[t];   // EnsureStreamHeaderWritten  :148-157
-            chunk_header(dst + pos, t, shrink, pl, sl.crc[c]);
-            team_copy(dst + pos + SNP_CHUNK_HEADER_LEN, shrink ? comp + sl.coff[c] : stage + sl.in_off[c], pl, t, team);
+            emit_slot(dst + pos, sl.rw(), c, stage, comp, t, team);
         }
     }
 }
@@ -351,24 +315,16 @@ SpliceWork work_layout(void* base, u32 nstreams, u32 max_slots, u64 stage_cap, u
     for (u64** p : {&w.st.aslots, &w.st.abytes, &w.st.nfirst, &w.st.gfirst}) *p = k.take<u64>(ns + 1);
     for (u32** p : {&w.st.flags, &w.st.hl, &w.st.tl, &w.st.e0, &w.st.e1}) *p = k.take<u32>(ns);
     w.st.fail = k.take<i32>(ns);
-    w.sl.in_off = k.take<u64>(M);
-    w.sl.coff = k.take<u64>(M);
-    w.sl.len = k.take<u32>(M);
-    w.sl.stream = k.take<u32>(M);
-    w.sl.comp_len = k.take<u32>(M);
-    w.sl.crc = k.take<u32>(M);
-    w.sl.c_status = k.take<i32>(M);
+    w.sl = carve_rw_owned_slots(k, M);
     w.rows = carve_chunk_rows(k, 2 * ns);
     w.cscan = k.take<u64>(M + 1);
     // staging: per admitted stream its decoded edges and its region behind them, the streams back to back (+ slack for the compressor's vector
-    // loads).  Compressed staging: slot c at c * snp_comp_stride(chunk_bytes), as in frame_chunked.hip.
+    // loads).  Compressed staging: slot c at c * snp_comp_stride(chunk_bytes) (fc_stage_off).
     w.stage = k.take<u8>(stage_cap + 256);
     w.comp = k.take<u8>(M * snp_comp_stride(chunk_bytes));
     w.bytes = k.bytes();
     return w;
 }
-
-u32 groups_of(u64 n) { return static_cast<u32>((n + 255) / 256); }
 
 }  // namespace
 
@@ -419,12 +375,10 @@ snp_status snp_frame_splice_indexed_batch(snp_ctx* c, const uint8_t* in, const u
         }
     }
     if (ok && M) {
-        // CompressBlock of every piece and its masked CRC-32C: one launch each, from staging
         hipLaunchKernelGGL(k_fs_slots, dim3(mg), dim3(256), 0, s, a, w.st, admit, w.sl, snp_comp_stride(cb));
         ok = c->check(hipGetLastError(), "frame splice slots");
-        if (ok && stage_cap)
-            ok = c->launch_compress(w.stage, w.sl.in_off, w.sl.len, M, w.comp, w.sl.coff, w.sl.comp_len, w.sl.c_status, 1) &&
-                 c->check(snp_launch_crc32c(w.stage, w.sl.in_off, w.sl.len, M, 1 | c->crc_bits(), w.sl.crc, nullptr, nullptr, s), "frame splice crc");
+        // every piece compressed from staging; without staging every slot is empty (reencode_slots in two steps: the scan below runs either way)
+        if (ok && stage_cap) ok = compress_slots(c, w.stage, w.sl.rw(), M, w.comp, "frame splice");
     }
     // the framed sizes of the new chunks, every stream's verdict, its emit units and the rows of its new index
     ok = ok && c->check(launch_scan(ScanFramed{w.sl.len, w.sl.comp_len}, M, w.part, w.cscan, nullptr, s), "frame splice size scan");

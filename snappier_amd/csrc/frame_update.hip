@@ -20,21 +20,16 @@
 //   new_pos   (only when asked) one thread per index row: a search in its stream's slots
 // Nothing here allocates, reads back or synchronises: the call is capturable like the other _batch entry points.
 #include "capi_internal.h"
-#include "scan_tiles.h"
-#include "work_carver.h"
+#include "frame_rewrite_device.h"
 #include "frame_update_device.h"
 #include "../../include/snappier_hip_frame_update.h"
 
 namespace {
 
-constexpr u64 kNoFail = ~0ull;
 constexpr u32 kHead = 0x100u, kLast = 0x200u, kLive = 0x400u;       // request flags above the status byte: edges, r0 < r1
 constexpr u32 kNamed = 1u, kPassed = 2u, kWritten = 4u;             // stream flags
-constexpr u64 kUnit = 65536;                                        // bytes of an old stream one emit workgroup takes at a time
 constexpr u32 kOverlayPieces = 8;                                   // workgroups that share one request's bytes
 constexpr u32 kMaxGroups = 8192;                                    // grid of the grid-stride check
-constexpr u32 kEmitGroups = 2048;                                   // ... of the emit: 8 workgroups per CU
-constexpr u32 kRowGroups = 1u << 20;                                // ... of new_pos
 
 __device__ __forceinline__ u64 fail_key(u32 r, i32 status) { return (static_cast<u64>(r) << 8) | static_cast<u64>(status & 0xff); }
 
@@ -66,10 +61,6 @@ struct UpSlots {
     i32* c_status;
 };
 
-struct ScanWords {
-    const u64* __restrict__ src;
-    __device__ __forceinline__ u64 operator()(u64 i) const { return src[i]; }
-};
 struct ScanLive {
     const u32* __restrict__ flags;
     __device__ __forceinline__ u64 operator()(u64 i) const { return (flags[i] & kLive) != 0; }
@@ -77,20 +68,6 @@ struct ScanLive {
 struct ScanOld {
     const u32* __restrict__ old;
     __device__ __forceinline__ u64 operator()(u64 i) const { return old[i]; }
-};
-__device__ __forceinline__ u32 payload_of(u32 comp, u32 raw, bool* shrink)
-{
-    *shrink = comp < raw;                                               // CompressBlock  SnappyStreamCompressor.cs:212
-    return *shrink ? comp : raw;
-}
-struct ScanNew {
-    const u32* __restrict__ dec;
-    const u32* __restrict__ comp_len;
-    __device__ __forceinline__ u64 operator()(u64 i) const
-    {
-        bool shrink;
-        return dec[i] ? SNP_CHUNK_HEADER_LEN + payload_of(comp_len[i], dec[i], &shrink) : 0;
-    }
 };
 
 // admission in stream order: both sums only grow
@@ -254,13 +231,14 @@ __global__ __launch_bounds__(256) void k_fu_fail(u32 max_slots, ChunkRows rows, 
 {
     const u32 t = blockIdx.x * 256u + threadIdx.x;
     if (t >= max_slots || rows.tag[t] == kNone) return;
-    const i32 s = rows.status[t] != SNP_OK ? rows.status[t] : rows.out_len[t] != rows.out_cap[t] ? SNP_ERR_INCOMPLETE : SNP_OK;
+    const i32 s = row_verdict(rows, t);
     if (s != SNP_OK) atomic_min64(st.fail + sl.stream[t], fail_key(sl.req[t], s));
 }
 
 // len bytes by the 256 threads of a workgroup, src and dst apart and misaligned differently for every run: the destination is brought to a
-// 16-byte boundary by byte stores, then aligned 16-byte stores from unaligned 16-byte loads (team_copy of frame_chunked.hip).  All threads
-// must call it.
+// 16-byte boundary by byte stores, then aligned 16-byte stores from unaligned 16-byte loads: team_copy (frame_chunked_device.h) with T = 256
+// and a 64-bit length.  It stays: with team_copy in its place k_fu_overlay came out at 338 instructions for 276 and k_fu_emit at 472 for 402
+// (profiles/r21a_refactor_kernel_stats.md).  All threads must call it.
 __device__ __forceinline__ void wg_copy(u8* dst, const u8* src, u64 len, u32 t)
 {
     if (len < 64) {
@@ -374,11 +352,7 @@ __global__ __launch_bounds__(256) void k_fu_emit(UpArgs a, UpStreams st, UpSlots
                     bool shrink;
                     const u32 pl = payload_of(sl.comp_len[j], d, &shrink);
                     u8* const at = dst + next + shift;
-                    if (tid < SNP_CHUNK_HEADER_LEN) {
-                        const u32 bs = pl + 4;                          // SnappyStreamCompressor.cs:236,251
-                        const u32 v = tid == 0 ? (shrink ? 0u : 1u) : tid < 4 ? (bs >> (8 * (tid - 1))) : (sl.crc[j] >> (8 * (tid - 4)));
-                        at[tid] = static_cast<u8>(v);
-                    }
+                    chunk_header(at, tid, shrink ? 0u : 1u, pl, sl.crc[j]);
                     wg_copy(at + SNP_CHUNK_HEADER_LEN, shrink ? comp + sl.coff[j] : raw + sl.place[j], pl, tid);
                 }
                 const u64 end = next + sl.old[j];
@@ -469,8 +443,6 @@ UpdateWork work_layout(void* base, u32 nstreams, u32 nreq, u32 max_slots, u64 st
     return w;
 }
 
-u32 groups_of(u64 n) { return static_cast<u32>((n + 255) / 256); }
-
 }  // namespace
 
 extern "C" {
@@ -531,11 +503,10 @@ snp_status snp_frame_write_indexed_batch(snp_ctx* c, const uint8_t* in, const ui
         if (ok) {
             hipLaunchKernelGGL(k_fu_fail, dim3(mg), dim3(256), 0, s, M, w.rows, w.sl, w.st);
             hipLaunchKernelGGL(k_fu_overlay, dim3(nreq, kOverlayPieces), dim3(256), 0, s, a, w.rq, w.st, admit, src, src_off, w.raw);
-            // CompressBlock of every slot's new bytes and their masked CRC-32C: one launch each, as in frame_chunked.hip
+            // every slot's new bytes re-encoded from the raw staging (reencode_slots), the new chunk sizes scanned into nscan
             ok = c->check(hipGetLastError(), "frame update overlay") &&
-                 c->launch_compress(w.raw, w.sl.place, w.sl.dec, M, w.comp, w.sl.coff, w.sl.comp_len, w.sl.c_status, 1) &&
-                 c->check(snp_launch_crc32c(w.raw, w.sl.place, w.sl.dec, M, 1 | c->crc_bits(), w.sl.crc, nullptr, nullptr, s), "frame update crc") &&
-                 c->check(launch_scan(ScanNew{w.sl.dec, w.sl.comp_len}, M, w.part, w.sl.nscan, nullptr, s), "frame update size scan") &&
+                 reencode_slots(c, w.raw, RwSlots{w.sl.place, w.sl.coff, w.sl.dec, w.sl.comp_len, w.sl.crc, w.sl.c_status}, M, w.comp, w.part, w.sl.nscan,
+                                "frame update") &&
                  c->check(launch_scan(ScanOld{w.sl.old}, M, w.part, w.sl.oscan, nullptr, s), "frame update old size scan");
         }
     }

@@ -96,11 +96,7 @@ __global__ __launch_bounds__(256) void k_frame_emit(const u8* __restrict__ raw, 
     const u64 o = dst_off[c];
     const u32 pl = payload[c];
     const u32 t = type[c];
-    if (tid < 8) {
-        const u32 bs = pl + 4;                                          // :236,251
-        const u32 v = tid == 0 ? t : tid < 4 ? (bs >> (8 * (tid - 1))) : (crc[c] >> (8 * (tid - 4)));
-        dst[o + tid] = static_cast<u8>(v);
-    }
+    chunk_header(dst + o, tid, t, pl, crc[c]);
     const u8* src = t == 0 ? comp + comp_off[c] : raw + in_off[c];
     block_copy(dst + o + SNP_CHUNK_HEADER_LEN, src, pl, tid);
 }

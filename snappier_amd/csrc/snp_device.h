@@ -122,6 +122,17 @@ __device__ __forceinline__ void block_copy(u8* dst, const u8* src, u32 len, u32 
 // Framing mask  Crc32CAlgorithm.ApplyMask  (Snappier/Internal/Crc32CAlgorithm.cs:156-158)
 __host__ __device__ __forceinline__ u32 crc32c_mask(u32 x) { return ((x >> 15) | (x << 17)) + 0xa282ead8u; }
 
+// The eight header bytes of a framed chunk, [type:1][len:3 LE = payload + 4][masked crc:4 LE], by the first 8 threads of a team (t: the
+// thread's place in it).  type: 0 compressed, 1 uncompressed.  The one writer of the format: every emit kernel calls it.
+__device__ __forceinline__ void chunk_header(u8* at, u32 t, u32 type, u32 pl, u32 crc)
+{
+    if (t < SNP_CHUNK_HEADER_LEN) {
+        const u32 bs = pl + 4;                                          // SnappyStreamCompressor.cs:236,251
+        const u32 v = t == 0 ? type : t < 4 ? (bs >> (8 * (t - 1))) : (crc >> (8 * (t - 4)));
+        at[t] = static_cast<u8>(v);
+    }
+}
+
 // A few control words set to zero ON THE STREAM.  Not hipMemsetAsync: as a node of a captured hipGraph a 4-byte memset runs on the first launch of the
 // graph only (ROCm 7.0, scripts/probe_graph_memset.py), and the batch entry points are meant to be capturable (tests/test_gpu_graph_capture.py).
 namespace {

@@ -57,6 +57,25 @@ def content(n: int, cb: int, seed: int) -> bytes:
     return b"".join(out)[:n]
 
 
+# Chunk sizes at which the emit kernels of the rewrite calls (update, append, splice, rechunk, compose) run teams of 64, 128 and 256 threads
+# (frame_chunked_device.h: fc_team(fc_group(cb))).
+TEAM_CHUNK_SIZES = [1000, 32768, 65536]
+
+
+@functools.lru_cache(maxsize=None)
+def team_blobs(cb: int):
+    """Three buffers of at most four chunks for the rewrite calls' team-size cases: random bytes (every chunk stays raw, tail of 7 bytes), a
+    repeated 64-byte pattern (every chunk compresses, no short tail) and corpus bytes (a short tail)."""
+    corpus, rnd = _pools()
+    pattern = bytes(range(64, 128))
+    return [rnd[11:11 + 3 * cb + 7], (pattern * (4 * cb // 64 + 1))[:4 * cb], corpus[:2 * cb + cb // 3]]
+
+
+def chunk_types(stream: bytes):
+    """The types of the non-empty data chunks of a framed stream: 0 compressed, 1 raw."""
+    return {r[0] for r in R.walk(stream)[0] if r[5] > 0}
+
+
 def windows(n: int, cb: int):
     """(offset, length): on a chunk boundary, one byte either side of it, inside one chunk, across three chunks, at the tail -- and past it."""
     return [(cb, cb), (cb - 1, 2), (1, max(cb - 2, 1)), (cb // 2, 2 * cb + (cb == 1)), (max(n - cb - 1, 0), cb + 5), (n, 3), (0, 1 << 62)]

@@ -15,6 +15,7 @@ import frame_chunked_model as K
 import frame_index_model as X
 import frame_range_model as R
 import oracle as O
+import seekable_cases as SC
 from append_harness import Appended, arena_of
 from conftest import read_testdata
 from seekable_harness import CANARY, Guarded, index_call, index_tensors
@@ -433,3 +434,16 @@ def test_one_stream_past_4_gib(html):
     rl, rs, _ = cd.frame_read_indexed(buf, H.dev([0]), new_len, new_ix, torch.zeros(1, dtype=torch.int32, device="cuda"), H.dev([len(old)]),
                                       H.dev([len(src)]), back, H.dev([0]), H.dev([len(src)]))
     assert rs.tolist() == [O.OK] and rl.tolist() == [len(src)] and torch.equal(back, data)
+
+
+# ---- rebuilt chunks stored compressed and stored raw, at the chunk sizes whose emit teams are 64, 128 and 256 threads --------------------------------
+@pytest.mark.parametrize("cb", SC.TEAM_CHUNK_SIZES)
+def test_rebuilt_chunks_raw_and_compressed_at_every_team_size(cb):
+    cd = SB.BlockCodec(0, O.HASH_CRC32C)
+    blobs = SC.team_blobs(cb)
+    streams = [K.stream_of(x, cb) for x in blobs]
+    srcs = [x[5:5 + cb + cb // 2] for x in blobs]                       # each stream's own kind of bytes: a reopened tail (0, 2) and fresh chunks
+    a = Appended(cd, streams, X.build_index(streams), srcs, cb).check()
+    assert a.got["status"] == [O.OK] * 3 and a.got["result"][2] == 2
+    assert a.after() == [K.stream_of(x + s, cb) for x, s in zip(blobs, srcs)]
+    assert [SC.chunk_types(s) for s in a.after()[:2]] == [{1}, {0}]

@@ -20,6 +20,7 @@ import frame_rechunk_model as RC
 import frame_splice_model as S
 import layouts
 import oracle as O
+import seekable_cases as SC
 from append_harness import arena_of
 from compose_harness import Composed, seg_tensors
 from conftest import read_testdata
@@ -530,3 +531,16 @@ def test_a_kept_chunk_whose_source_position_lies_past_2_to_the_32(html):
     first = len(K.chunks_of(piece[100:], cb)[0])
     assert new_ix.first.tolist() == [0, 3] and new_ix.start[:3].tolist() == [0, cb - 100, 2 * cb - 100]
     assert new_ix.pos[:3].tolist() == [10, 10 + first, 10 + first + len(one)] and new_ix.total.tolist() == [2 * cb]
+
+
+# ---- rebuilt chunks stored compressed and stored raw, at the chunk sizes whose emit teams are 64, 128 and 256 threads --------------------------------
+@pytest.mark.parametrize("cb", SC.TEAM_CHUNK_SIZES)
+def test_rebuilt_chunks_raw_and_compressed_at_every_team_size(cb):
+    cd = SB.BlockCodec(0, O.HASH_CRC32C)
+    blobs = SC.team_blobs(cb)
+    streams = [K.stream_of(x, cb) for x in blobs]
+    outputs = [[(b, 5, len(x) - 9)] for b, x in enumerate(blobs)]       # a segment that cuts its first and its last chunk: two pieces, kept chunks between
+    cp = Composed(cd, streams, X.build_index(streams), CM.seg_lists(outputs), cb).check()
+    assert cp.got["status"] == [O.OK] * 3 and cp.got["result"][3] == 3
+    assert [O.frame_decode(s) for s in cp.written()] == [x[5:len(x) - 4] for x in blobs]
+    assert [SC.chunk_types(s) for s in cp.written()[:2]] == [{1}, {0}]

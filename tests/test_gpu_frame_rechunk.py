@@ -18,6 +18,7 @@ import frame_rechunk_model as RC
 import frame_splice_model as S
 import layouts
 import oracle as O
+import seekable_cases as SC
 from append_harness import arena_of
 from conftest import read_testdata
 from rechunk_harness import Rechunked, new_table
@@ -488,3 +489,15 @@ def test_a_kept_prefix_that_ends_past_position_2_to_the_32(html):
     rl, rs, _ = cd.frame_read_indexed(out, H.dev([0]), out_len, new_ix, torch.zeros(1, dtype=torch.int32, device="cuda"), H.dev([nkept * cb]),
                                       H.dev([len(tail_raw)]), back, H.dev([0]), H.dev([len(tail_raw)]))
     assert rs.tolist() == [O.OK] and rl.tolist() == [len(tail_raw)] and back.cpu().numpy().tobytes() == tail_raw
+
+
+# ---- rebuilt chunks stored compressed and stored raw, at the chunk sizes whose emit teams are 64, 128 and 256 threads --------------------------------
+@pytest.mark.parametrize("cb", SC.TEAM_CHUNK_SIZES)
+def test_rebuilt_chunks_raw_and_compressed_at_every_team_size(cb):
+    cd = SB.BlockCodec(0, O.HASH_CRC32C)
+    blobs = SC.team_blobs(cb)
+    streams = [K.stream_of(x, cb // 2 + 1) for x in blobs]              # no old chunk but the first ends on a boundary of the new ones
+    rc = Rechunked(cd, streams, X.build_index(streams), cb).check()
+    assert rc.got["status"] == [O.OK] * 3 and rc.got["result"][3] == 3
+    assert rc.after() == [K.stream_of(x, cb) for x in blobs]
+    assert [SC.chunk_types(s) for s in rc.after()[:2]] == [{1}, {0}]

@@ -15,6 +15,7 @@ import frame_index_model as X
 import frame_range_model as R
 import frame_splice_model as S
 import oracle as O
+import seekable_cases as SC
 from append_harness import arena_of
 from conftest import read_testdata
 from seekable_harness import CANARY, Guarded, index_call, index_tensors
@@ -471,3 +472,17 @@ def test_a_hole_past_position_2_to_the_32(html):
     rl, rs, _ = cd.frame_read_indexed(out, H.dev([0]), out_len, new_ix, torch.zeros(1, dtype=torch.int32, device="cuda"), H.dev([req[0]]),
                                       H.dev([len(src)]), back, H.dev([0]), H.dev([len(src)]))
     assert rs.tolist() == [O.OK] and rl.tolist() == [len(src)] and torch.equal(back, data)
+
+
+# ---- rebuilt chunks stored compressed and stored raw, at the chunk sizes whose emit teams are 64, 128 and 256 threads --------------------------------
+@pytest.mark.parametrize("cb", SC.TEAM_CHUNK_SIZES)
+def test_rebuilt_chunks_raw_and_compressed_at_every_team_size(cb):
+    cd = SB.BlockCodec(0, O.HASH_CRC32C)
+    blobs = SC.team_blobs(cb)
+    streams = [K.stream_of(x, cb) for x in blobs]
+    reqs = [(cb - 3, 10)] * 3                                           # a hole across the first chunk boundary: a head and a tail edge
+    srcs = [x[5:5 + cb + 5] for x in blobs]                             # each stream's own kind of bytes
+    sp = Spliced(cd, streams, X.build_index(streams), reqs, srcs, cb).check()
+    assert sp.got["status"] == [O.OK] * 3 and sp.got["result"][3] == 3
+    assert [O.frame_decode(s) for s in sp.got["streams"]] == [S.edited(x, off, dele, src) for x, (off, dele), src in zip(blobs, reqs, srcs)]
+    assert [SC.chunk_types(s) for s in sp.got["streams"][:2]] == [{1}, {0}]

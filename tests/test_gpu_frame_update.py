@@ -15,6 +15,7 @@ import frame_index_model as X
 import frame_range_model as R
 import frame_update_model as U
 import oracle as O
+import seekable_cases as SC
 from conftest import read_testdata
 from seekable_harness import CANARY, Guarded, Updated, index_tensors
 
@@ -391,3 +392,17 @@ def test_update_to_memory(html):
     assert g_st.tolist() == [O.OK, O.OK]
     g = got.cpu().numpy()
     assert g[:8300].tobytes() == srcs[0] and g[int(g_off[1]):int(g_off[1]) + 1].tobytes() == srcs[2]
+
+
+# ---- rebuilt chunks stored compressed and stored raw, at the chunk sizes whose emit teams are 64, 128 and 256 threads --------------------------------
+@pytest.mark.parametrize("cb", SC.TEAM_CHUNK_SIZES)
+def test_rebuilt_chunks_raw_and_compressed_at_every_team_size(cb):
+    cd = SB.BlockCodec(0, O.HASH_CRC32C)
+    blobs = SC.team_blobs(cb)
+    streams, ix = batch_of(blobs, cb, O.HASH_CRC32C)
+    reqs = [(b, cb - 3, cb + 10) for b in range(3)]                    # a tail edge, a whole chunk and a head edge in every stream
+    srcs = [x[5:5 + cb + 10] for x in blobs]                            # each stream's own kind of bytes
+    u = Updated(cd, streams, ix, reqs, srcs).check()
+    assert u.got["status"] == [O.OK] * 3 and u.got["result"][0] == 9
+    assert u.got["streams"] == [K.stream_of(U.patched(x, reqs, srcs, b), cb) for b, x in enumerate(blobs)]
+    assert [SC.chunk_types(s) for s in u.got["streams"][:2]] == [{1}, {0}]
