@@ -24,6 +24,8 @@ BLOCK_SIZE = 65536
 MAX_BLOCK_COMPRESSED = 76491
 RECHUNK_REWRITE_ALL = 1                  # SNP_RECHUNK_REWRITE_ALL (include/snappier_hip_frame_rechunk.h)
 DIFF_PREFIX, DIFF_SUFFIX, DIFF_EXACT = 1, 2, 4   # SNP_DIFF_PREFIX, SNP_DIFF_SUFFIX, SNP_DIFF_EXACT (include/snappier_hip_frame_diff.h)
+FIND_MAX_NEEDLE = 256    # SNP_FIND_MAX_NEEDLE (include/snappier_hip_frame_find.h)
+FIND_TILE = 16384        # kFindTile (csrc/frame_find_device.h): the start positions one workgroup step of the find takes
 # snp_option (include/snappier_hip.h)
 (OPT_DECODE_LAYOUT, OPT_SMALL_BLOCK_MAX, OPT_SMALL_BLOCK_MIN_BATCH, OPT_COMPRESS_LAYOUT, OPT_COMPRESS_WINDOW_MAX_BATCH,
  OPT_TABLE_PROBE_TRIES, OPT_TABLE_PROBE_MAX_BYTES, OPT_PARALLEL_DECODE_MIN, OPT_FENCED, OPT_DECODE_LEFTOVERS, OPT_CRC_KERNEL,
@@ -211,6 +213,11 @@ _EXTENSIONS = {
         "snp_frame_diff_indexed_workspace": (_u64, [_u32, _u64, _u64]),
         "snp_frame_diff_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch find: where a byte string occurs in windows of what seekable framed streams decode to -- the windows' chunks decoded into scratch and searched there
+    "frame_find": ("libsnappier_hip_frame_find.so", "snappier_hip_frame_find.h", {
+        "snp_frame_find_indexed_workspace": (_u64, [_u32, _u64, _u64]),
+        "snp_frame_find_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _u64,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -259,6 +266,7 @@ FRAME_RECHUNK_PATH = _extension_path("frame_rechunk")
 FRAME_COMPOSE_PATH = _extension_path("frame_compose")
 FRAME_DIGEST_PATH = _extension_path("frame_digest")
 FRAME_DIFF_PATH = _extension_path("frame_diff")
+FRAME_FIND_PATH = _extension_path("frame_find")
 
 
 def buffers_lib() -> C.CDLL:
@@ -331,6 +339,11 @@ def frame_diff_lib() -> C.CDLL:
     return _extension("frame_diff")
 
 
+def frame_find_lib() -> C.CDLL:
+    """libsnappier_hip_frame_find.so (include/snappier_hip_frame_find.h)."""
+    return _extension("frame_find")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -385,6 +398,10 @@ def frame_digest_declared_symbols() -> list[str]:
 
 def frame_diff_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_diff"))
+
+
+def frame_find_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_find"))
 
 
 def status_string(st: int) -> str:

@@ -5,6 +5,7 @@ torch is plumbing here (allocation, streams, torch.distributed); the work is don
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 
 import torch
 
@@ -1040,6 +1041,163 @@ class BlockCodec:
         """
         prefix, suffix, len_a, len_b, status = self.frame_diff_streams(a, b)
         return prefix, len_a - prefix - suffix, prefix.clone(), len_b - prefix - suffix, status
+
+    def _needle_tensors(self, needles, nreq: int):
+        """One needle for all requests (bytes), one per request (a list of bytes), or the three device tensors themselves
+        (bytes uint8, needle_off int64, needle_len int32): -> those three tensors."""
+        if isinstance(needles, tuple):
+            return needles
+        if isinstance(needles, (bytes, bytearray)):
+            data, off, ln = bytes(needles), [0] * nreq, [len(needles)] * nreq
+        else:
+            if len(needles) != nreq:
+                raise ValueError("frame_find_indexed: one needle per request")
+            ln = [len(x) for x in needles]
+            off = [0, *itertools.accumulate(ln[:-1])][:nreq]
+            data = b"".join(needles)
+        host = torch.frombuffer(bytearray(data or b"\0"), dtype=torch.uint8)
+        return (host.to(self.device), torch.tensor(off, dtype=torch.int64).to(self.device), torch.tensor(ln, dtype=torch.int32).to(self.device))
+
+    def frame_find_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", req_stream: torch.Tensor,
+                           req_off: torch.Tensor, req_len: torch.Tensor, needles, hit_cap, max_rows: int | None = None,
+                           scratch_cap: int | None = None, work: torch.Tensor | None = None):
+        """Where a byte string occurs in windows of what framed streams decode to: -> (status, win_len, count, nhits, hits, hit_off), the
+        positions in hits AS OFFSETS INTO WHAT THE STREAM DECODES TO, not into the window.  frame_find_indexed_result, which says the rest,
+        without the d_result."""
+        return self.frame_find_indexed_result(framed, in_off, in_len, index, req_stream, req_off, req_len, needles, hit_cap, max_rows, scratch_cap,
+                                              work)[:6]
+
+    def frame_find_indexed_result(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex",
+                                  req_stream: torch.Tensor, req_off: torch.Tensor, req_len: torch.Tensor, needles, hit_cap,
+                                  max_rows: int | None = None, scratch_cap: int | None = None, work: torch.Tensor | None = None):
+        """Where a byte string occurs in windows of what framed streams decode to (snp_frame_find_indexed_batch,
+        libsnappier_hip_frame_find.so): -> (status, win_len, count, nhits, hits, hit_off, result); frame_find_indexed gives the first six.
+
+        Request r searches the window [req_off[r], +req_len[r]) of what stream req_stream[r] (int32) decodes to (int64 tensors, read as
+        unsigned; offset 0 and length -1 is the whole stream) for its needle: `needles` is one bytes for all requests, a list with one per
+        request (1 to FIND_MAX_NEEDLE bytes each), or the three device tensors (bytes, needle_off int64, needle_len int32) themselves.
+        hit_cap is one int for all requests or an int64 tensor; hit_off is its exclusive prefix sum.  count[r] is the number of all
+        occurrences in the window, overlapping ones included; hits[hit_off[r] .. +nhits[r]) holds the first nhits[r] = min(count[r],
+        hit_cap[r]) of them in ascending order.  THE POSITIONS ARE OFFSETS INTO WHAT THE STREAM DECODES TO, not into the window, so they go
+        straight into req_off of frame_read_indexed and sp_off of the splice.  win_len is the clipped window's length; status is what
+        frame_read_indexed gives for the same window.  A request that is not OK has win_len = count = nhits = 0.  Every chunk the window
+        meets is decoded whole, into scratch inside the workspace, and verified (include/snappier_hip_frame_find.h).  result is the
+        4-element int64 d_result: [0] = rows needed, [1] = sum of count over the OK requests, [2] = scratch bytes needed, [3] = requests that
+        are OK.  Record boundaries, then the records:
+
+            st, wl, count, nhits, hits, hit_off = cd.frame_find_indexed(framed, in_off, in_len, index, req_stream, req_off, req_len, b"\\n", cap)
+            ends = hits[: int(nhits[0])]                       # request 0: the offset of every delimiter in its window
+            starts = torch.cat([req_off[:1], ends[:-1] + 1])   # a record lies between two delimiters
+            cd.frame_read_indexed(framed, in_off, in_len, index, req_stream[:1].expand(len(ends)).contiguous(), starts, ends - starts, out, ...)
+
+        Default bounds: one sizing call (max_rows = scratch_cap = 0) and a synchronising read of its d_result, then the real call unless the
+        sizing call already was one.  A caller that passes both bounds, work, an int hit_cap and needle tensors enqueues only."""
+        self._bind()
+        nreq, ns = req_stream.numel(), in_len.numel()
+        if req_stream.dtype != torch.int32:
+            raise ValueError("frame_find_indexed: req_stream must be an int32 tensor")
+        FL = N.frame_find_lib()
+        nd, nd_off, nd_len = self._needle_tensors(needles, nreq)
+        if isinstance(hit_cap, int):
+            total = nreq * hit_cap
+            hit_off = torch.arange(nreq, dtype=torch.int64, device=self.device) * hit_cap
+            hit_cap = torch.full((nreq,), hit_cap, dtype=torch.int64, device=self.device)
+        else:
+            hit_off = torch.cumsum(hit_cap, 0) - hit_cap
+            total = int(hit_cap.sum().item()) if nreq else 0
+        hits = torch.empty(max(total, 1), dtype=torch.int64, device=self.device)
+        framed = self._readable(framed, nreq)
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+        win_len, count, nhits = (torch.empty(nreq, dtype=torch.int64, device=self.device) for _ in range(3))
+        status = torch.empty(nreq, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+
+        def call(mr: int, sc: int, w: torch.Tensor | None):
+            w = self._work("frame_find_indexed", w, FL.snp_frame_find_indexed_workspace, nreq, mr, sc)
+            st = FL.snp_frame_find_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                                 _p(index.total), _p(index.tail), index.nentries, _p(req_stream), _p(req_off), _p(req_len), nreq,
+                                                 _p(nd), _p(nd_off), _p(nd_len), mr, sc, _p(hits), _p(hit_off), _p(hit_cap), _p(win_len), _p(count),
+                                                 _p(nhits), _p(status), _p(w), _p(result))
+            raise_for_status(st, self.ctx.handle)
+
+        sized = False
+        if max_rows is None or scratch_cap is None:
+            call(0 if max_rows is None else max_rows, 0 if scratch_cap is None else scratch_cap, None)
+            need = [v & 0xFFFFFFFFFFFFFFFF for v in result.tolist()]
+            sized = need[0] == 0 and need[2] == 0
+            max_rows = min(need[0], (1 << 31) - 1) if max_rows is None else max_rows
+            scratch_cap = need[2] if scratch_cap is None else scratch_cap
+        if not sized:
+            call(max_rows, scratch_cap, work)
+        return status, win_len, count, nhits, hits, hit_off, result
+
+    def frame_find_streams(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", needle: bytes,
+                           max_hits: int | None = None, scratch_bytes: int = 256 << 20):
+        """Every occurrence of `needle` in every stream, or the first max_hits per stream: -> (count, hits, status) -- count an int64 tensor
+        with each stream's number of occurrences (all of them, whatever max_hits), hits a list with one int64 tensor of ascending positions
+        per stream, status an int32 tensor with the first status that is not OK among a stream's windows (a stream that is not OK has count
+        0 and no hits).  THE POSITIONS ARE OFFSETS INTO WHAT THE STREAM DECODES TO.
+
+        The streams are cut into windows [k T, k T + T + m - 1), m = len(needle): an occurrence starts in [k T, k T + T) exactly when it lies
+        inside that window, so the windows' hits, one after the other, are the stream's.  Windows are batched so that a call's scratch stays
+        under scratch_bytes (a single window that needs more gets what it needs).  T is a multiple of 65536, so a window's first chunk is
+        decoded twice only where the stream's chunks do not end on multiples of 65536 (a foreign stream, or one after a splice); its last
+        chunk -- the one that holds the m - 1 bytes past k T + T -- is decoded again by the next window whenever m > 1.
+        It reads idx_total and d_result back, so it is not capturable."""
+        m, ns = len(needle), in_len.numel()
+        if not 1 <= m <= N.FIND_MAX_NEEDLE:
+            raise ValueError("frame_find_streams: the needle must have 1 to %d bytes" % N.FIND_MAX_NEEDLE)
+        totals = index.total.tolist()
+        T = max(65536, scratch_bytes // 2 // 65536 * 65536)
+        wins = [(b, k * T, min(T + m - 1, totals[b] - k * T)) for b in range(ns) for k in range(max((max(totals[b] - m, -1) + T) // T, 1))]
+        count = [0] * ns
+        status = [0] * ns
+        parts = [[] for _ in range(ns)]
+        have = [0] * ns
+        limit = (1 << 62) if max_hits is None else max_hits
+        at = 0
+        while at < len(wins):
+            n, used = 0, 0
+            while at + n < len(wins) and (n == 0 or used + wins[at + n][2] <= scratch_bytes):
+                used += wins[at + n][2]
+                n += 1
+            while True:
+                batch = wins[at:at + n]
+                rs = torch.tensor([w[0] for w in batch], dtype=torch.int32).to(self.device)
+                ro = torch.tensor([w[1] for w in batch], dtype=torch.int64).to(self.device)
+                rl = torch.tensor([w[2] for w in batch], dtype=torch.int64).to(self.device)
+                caps = [min(max(limit - have[w[0]], 0), max(1024, w[2] // 64)) for w in batch]
+                cap_t = torch.tensor(caps, dtype=torch.int64).to(self.device)
+                sizing = self.frame_find_indexed_result(framed, in_off, in_len, index, rs, ro, rl, needle, cap_t, 0, 0)
+                need = [v & 0xFFFFFFFFFFFFFFFF for v in sizing[6].tolist()]
+                if need[2] <= scratch_bytes or n == 1:
+                    break
+                n = max(1, min(n - 1, n * scratch_bytes // need[2]))
+            st, _, cnt, nh, hits, hit_off = self.frame_find_indexed(framed, in_off, in_len, index, rs, ro, rl, needle, cap_t,
+                                                                    min(need[0], (1 << 31) - 1), need[2])
+            st, cnt, nh, off = st.tolist(), cnt.tolist(), nh.tolist(), hit_off.tolist()
+            again = [i for i in range(n) if st[i] == 0 and nh[i] < min(cnt[i], max(limit - have[batch[i][0]], 0))]
+            found = {i: hits[off[i]:off[i] + nh[i]] for i in range(n) if i not in again}
+            if again:                                                   # more hits than the guess: those windows once more, with room for all
+                pick = torch.tensor(again, dtype=torch.int64).to(self.device)
+                cap2 = torch.tensor([min(cnt[i], max(limit - have[batch[i][0]], 0)) for i in again], dtype=torch.int64).to(self.device)
+                _, _, _, nh2, hits2, off2 = self.frame_find_indexed(framed, in_off, in_len, index, rs[pick], ro[pick], rl[pick], needle, cap2)
+                nh2, off2 = nh2.tolist(), off2.tolist()
+                found.update({i: hits2[off2[j]:off2[j] + nh2[j]] for j, i in enumerate(again)})
+            for i, (b, _, _) in enumerate(batch):
+                if st[i] != 0:
+                    status[b] = status[b] or st[i]
+                    continue
+                count[b] += cnt[i]
+                take = found[i][:max(limit - have[b], 0)]
+                if take.numel():
+                    parts[b].append(take.clone())
+                    have[b] += take.numel()
+            at += n
+        empty = torch.empty(0, dtype=torch.int64, device=self.device)
+        hits = [empty if status[b] or not parts[b] else torch.cat(parts[b]) for b in range(ns)]
+        count = [0 if status[b] else count[b] for b in range(ns)]
+        return (torch.tensor(count, dtype=torch.int64).to(self.device), hits, torch.tensor(status, dtype=torch.int32).to(self.device))
 
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()

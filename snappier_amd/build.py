@@ -5,7 +5,7 @@
                                             # libsnappier_hip_frame_index.so, libsnappier_hip_frame_chunked.so, libsnappier_hip_frame_update.so,
                                             # libsnappier_hip_frame_append.so, libsnappier_hip_frame_splice.so, libsnappier_hip_frame_rechunk.so,
                                             # libsnappier_hip_frame_compose.so, libsnappier_hip_frame_digest.so,
-                                            # libsnappier_hip_frame_diff.so
+                                            # libsnappier_hip_frame_diff.so, libsnappier_hip_frame_find.so
                                             # (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
@@ -51,6 +51,8 @@ LIBS = {
     "libsnappier_hip_frame_digest.so": ["frame_digest.hip"],
     # include/snappier_hip_frame_diff.h: device batch diff (common prefix and suffix of decoded windows) of seekable framed streams, header CRCs between common chunk boundaries -- the same kind of extension
     "libsnappier_hip_frame_diff.so": ["frame_diff.hip"],
+    # include/snappier_hip_frame_find.h: device batch find (where a byte string occurs in decoded windows) of seekable framed streams, the windows' chunks decoded into scratch -- the same kind of extension
+    "libsnappier_hip_frame_find.so": ["frame_find.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 # every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)
