@@ -24,7 +24,7 @@ extern "C" {
  * [sp_off[b], sp_off[b] + sp_del[b]) are replaced by src[src_off[b] .. +sp_ins[b]).  Insert is del = 0, delete is ins = 0, truncate is
  * del = idx_total[b] - off, drop-prefix is off = 0.  Several edits of one stream are several calls: the new index goes straight into the next
  * one, and no synchronisation is needed between them.  A SORTED REQUEST LIST WITH SEVERAL SPLICES PER STREAM IS DELIBERATELY NOT PART OF THIS
- * CALL: merging the rewritten regions of neighbouring requests would double the planning.
+ * CALL: merging the rewritten regions of neighbouring requests would double the planning.  (snp_frame_edit_indexed_batch, snappier_hip_frame_edit.h, is that call.)
  * Out of place, like the update call: `in`, `src` and the old index are only read; the new stream of b goes to out[out_off[b] .. +out_cap[b]),
  * which must not overlap `in`.
  *

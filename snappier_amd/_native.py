@@ -218,6 +218,11 @@ _EXTENSIONS = {
         "snp_frame_find_indexed_workspace": (_u64, [_u32, _u64, _u64]),
         "snp_frame_find_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _u64,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch edit: a sorted edit script per seekable framed stream -- each touched chunk decoded once, each rewritten region compressed once, the new index
+    "frame_edit": ("libsnappier_hip_frame_edit.so", "snappier_hip_frame_edit.h", {
+        "snp_frame_edit_indexed_workspace": (_u64, [_u32, _u32, _u32, _u64, _u32]),
+        "snp_frame_edit_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32,
+                                                _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -267,6 +272,7 @@ FRAME_COMPOSE_PATH = _extension_path("frame_compose")
 FRAME_DIGEST_PATH = _extension_path("frame_digest")
 FRAME_DIFF_PATH = _extension_path("frame_diff")
 FRAME_FIND_PATH = _extension_path("frame_find")
+FRAME_EDIT_PATH = _extension_path("frame_edit")
 
 
 def buffers_lib() -> C.CDLL:
@@ -344,6 +350,11 @@ def frame_find_lib() -> C.CDLL:
     return _extension("frame_find")
 
 
+def frame_edit_lib() -> C.CDLL:
+    """libsnappier_hip_frame_edit.so (include/snappier_hip_frame_edit.h)."""
+    return _extension("frame_edit")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -402,6 +413,10 @@ def frame_diff_declared_symbols() -> list[str]:
 
 def frame_find_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_find"))
+
+
+def frame_edit_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_edit"))
 
 
 def status_string(st: int) -> str:

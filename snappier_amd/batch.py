@@ -1199,6 +1199,133 @@ class BlockCodec:
         count = [0 if status[b] else count[b] for b in range(ns)]
         return (torch.tensor(count, dtype=torch.int64).to(self.device), hits, torch.tensor(status, dtype=torch.int32).to(self.device))
 
+    def frame_edit_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", ed_first: torch.Tensor,
+                           ed_off: torch.Tensor, ed_del: torch.Tensor, data: torch.Tensor, data_off: torch.Tensor, data_len: torch.Tensor,
+                           chunk_bytes: int, out: torch.Tensor, out_off: torch.Tensor, out_cap: torch.Tensor, max_slots: int, stage_cap: int,
+                           work: torch.Tensor | None = None, with_bound: bool = False):
+        """A sorted EDIT SCRIPT per framed stream through its chunk index (snp_frame_edit_indexed_batch, libsnappier_hip_frame_edit.so):
+        -> (out_len, status, ed_status, FrameIndex, result) and, with_bound, out_bound behind them.  The direct call: it enqueues only (it
+        allocates its outputs, and the workspace when `work` is None).
+
+        Stream b has the edits [ed_first[b], ed_first[b + 1]) (int64, nstreams + 1 values: the form hit_off has coming out of
+        frame_find_indexed).  Edit e replaces bytes [ed_off[e], ed_off[e] + ed_del[e]) of what the OLD stream decodes to by
+        data[data_off[e] .. +data_len[e]) (int64 tensors, read as unsigned); the edits of a stream are ascending and disjoint, all in the old
+        stream's coordinates, and one with ed_del = data_len = 0 is skipped.  Each touched chunk is decoded once, each rewritten region
+        compressed once in pieces of chunk_bytes, every other kept byte copied once, and a stream is edited whole or not at all
+        (out_len[b] = 0 then: include/snappier_hip_frame_edit.h).  ed_status is each edit's own verdict (int32).  The outputs, the returned
+        FrameIndex (start / pos hold index.nentries + max_slots rows), result and the sizing call (max_slots = stage_cap = 0) are those of
+        frame_splice_indexed."""
+        if not 1 <= chunk_bytes <= N.BLOCK_SIZE:
+            raise ValueError(f"frame_edit_indexed: chunk_bytes = {chunk_bytes}, must be 1 .. {N.BLOCK_SIZE}")
+        self._bind()
+        ns, nedits = in_len.numel(), ed_off.numel()
+        if ed_first.numel() != ns + 1:
+            raise ValueError(f"frame_edit_indexed: ed_first holds {ed_first.numel()} values, {ns} streams need {ns + 1}")
+        EL = N.frame_edit_lib()
+        framed, out, data = self._readable(framed, ns), self._readable(out, ns), self._readable(data, ns)
+        ne = index.nentries
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+        out_len = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        status = torch.zeros(ns, dtype=torch.int32, device=self.device)
+        ed_status = torch.zeros(nedits, dtype=torch.int32, device=self.device)
+        first = torch.zeros(ns + 1, dtype=torch.int64, device=self.device)
+        rows = ne + max_slots
+        new_start = torch.empty(max(rows, 1), dtype=torch.int64, device=self.device)
+        new_pos = torch.empty(max(rows, 1), dtype=torch.int64, device=self.device)
+        total = torch.empty(ns, dtype=torch.int64, device=self.device)
+        tail = torch.empty(ns, dtype=torch.int32, device=self.device)
+        bound = torch.zeros(ns, dtype=torch.int64, device=self.device) if with_bound else None
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        w = self._work("frame_edit_indexed", work, EL.snp_frame_edit_indexed_workspace, ns, nedits, max_slots, stage_cap, chunk_bytes)
+        st = EL.snp_frame_edit_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                             _p(index.total), _p(index.tail), ne, _p(data), _p(ed_first), _p(ed_off), _p(ed_del), _p(data_len),
+                                             _p(data_off), nedits, chunk_bytes, max_slots, stage_cap, _p(out), _p(out_off), _p(out_cap),
+                                             _p(out_len), _p(status), _p(ed_status), _p(first), _p(new_start), _p(new_pos), _p(total), _p(tail),
+                                             _p(bound), _p(w), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        got = (out_len, status, ed_status, FrameIndex(first, new_start[:rows], new_pos[:rows], total, tail, result), result)
+        return got + (bound,) if with_bound else got
+
+    def frame_edit_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", ed_first: torch.Tensor,
+                             ed_off: torch.Tensor, ed_del: torch.Tensor, data: torch.Tensor, data_off: torch.Tensor, data_len: torch.Tensor,
+                             chunk_bytes: int = N.BLOCK_SIZE, align: int = 1, max_bytes: int | None = None):
+        """Edit framed streams given the framed tensor, its table, its index and an edit script per stream:
+        -> (out, out_off, out_len, status, ed_status, FrameIndex).
+
+        ONE sizing call (max_slots = stage_cap = 0, every out_cap 0) that also asks for each named stream's size bound, ONE synchronising read
+        of its result and of the arena size (ValueError if that is above max_bytes), an arena in which stream b's slot is its bound rounded up
+        to `align` (0 for a stream that is left alone or refused), then the edit.  Streams with out_len 0 are not in the arena: the caller
+        keeps their old bytes, and the returned index holds their old rows."""
+        ns = in_len.numel()
+        zero = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        empty = torch.empty(0, dtype=torch.uint8, device=self.device)
+        _, _, _, _, result, bound = self.frame_edit_indexed(framed, in_off, in_len, index, ed_first, ed_off, ed_del, data, data_off, data_len,
+                                                            chunk_bytes, empty, zero, zero, 0, 0, with_bound=True)
+        slot = (bound + (align - 1)) // align * align
+        ends = torch.cumsum(slot, 0)
+        out_off = ends - slot
+        need = torch.cat([result, ends[-1:] if ns else zero[:0].new_zeros(1)]).tolist()
+        if need[0] > 0xFFFFFFFF:
+            raise ValueError(f"frame_edit_to_memory: {need[0]} chunk slots, one call takes 2^32 - 1")
+        if max_bytes is not None and need[-1] > max_bytes:
+            raise ValueError(f"frame_edit_to_memory: the new streams take up to {need[-1]} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need[-1], 1), dtype=torch.uint8, device=self.device)
+        out_len, status, ed_status, new_index, _ = self.frame_edit_indexed(framed, in_off, in_len, index, ed_first, ed_off, ed_del, data, data_off,
+                                                                           data_len, chunk_bytes, out, out_off, bound, need[0], need[2])
+        return out[:need[-1]], out_off, out_len, status, ed_status, new_index
+
+    def frame_replace_streams(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", needle: bytes,
+                              replacement: bytes, chunk_bytes: int = N.BLOCK_SIZE):
+        """Every occurrence of `needle` in every stream replaced by `replacement`: -> (out, out_off, out_len, status, FrameIndex, count); a
+        written stream decodes to bytes.replace(needle, replacement) of what it decoded to, and count is each stream's number of
+        replacements.  frame_find_streams, then ONE frame_edit_to_memory with one edit per kept hit.
+
+        The find reports overlapping occurrences; bytes.replace takes the leftmost one and goes on behind it.  A needle without a proper
+        border (no prefix that is also a suffix) cannot overlap itself, and every hit is kept.  Otherwise the kept hits are those reached
+        from a stream's first hit by `the first hit at or behind this one's end`, found by pointer doubling over torch.searchsorted on the
+        device, not by a host loop over the hits.  A stream without a hit, and one whose find is not OK (its status is returned), is left
+        alone: out_len 0, its old rows in the index.  It reads results back between its steps, so it is not capturable."""
+        m, ns = len(needle), in_len.numel()
+        count, hits, fstatus = self.frame_find_streams(framed, in_off, in_len, index, needle)
+        counts = torch.tensor([h.numel() for h in hits], dtype=torch.int64).to(self.device)
+        ed_off = torch.cat(hits) if ns else counts.new_zeros(0)
+        if any(needle[:k] == needle[m - k:] for k in range(1, m)):
+            ed_off, counts = self._leftmost_disjoint(ed_off, counts, index.total, m)
+        ed_first = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
+        nedits = ed_off.numel()
+        ed_del = torch.full((nedits,), m, dtype=torch.int64, device=self.device)
+        data = torch.frombuffer(bytearray(replacement), dtype=torch.uint8).to(self.device) if replacement else torch.empty(0, dtype=torch.uint8, device=self.device)
+        data_off = torch.zeros(nedits, dtype=torch.int64, device=self.device)
+        data_len = torch.full((nedits,), len(replacement), dtype=torch.int64, device=self.device)
+        out, out_off, out_len, status, _, new_index = self.frame_edit_to_memory(framed, in_off, in_len, index, ed_first, ed_off, ed_del, data,
+                                                                                 data_off, data_len, chunk_bytes)
+        return out, out_off, out_len, torch.where(fstatus != 0, fstatus, status), new_index, counts
+
+    @staticmethod
+    def _leftmost_disjoint(hits: torch.Tensor, counts: torch.Tensor, total: torch.Tensor, m: int):
+        """Of the ascending positions of all occurrences of an m-byte needle -- `hits`, the streams' one behind the other, counts[b] of stream b,
+        which decodes to total[b] bytes -- the ones bytes.replace takes: a stream's first, then always the first at or behind the end of the
+        one before.  -> (the kept hits, their count per stream).  ONE pointer doubling for the whole batch: every hit points at the first hit of
+        its stream at or behind its end (one searchsorted over keys that set the streams apart), the end of a stream at a sentinel that points
+        at itself; log2(the most hits a stream has) rounds of `mark what the marked ones point at; point twice as far`."""
+        n = hits.numel()
+        if n < 2:
+            return hits, counts
+        span = total + (m + 1)                                          # stream b's keys lie in [base[b], base[b] + total[b]]: apart by more than m
+        keys = hits + torch.repeat_interleave(torch.cumsum(span, 0) - span, counts)
+        last = torch.cumsum(counts, 0)
+        ends = torch.repeat_interleave(last, counts)                    # where the hits of a hit's own stream end
+        jump = torch.searchsorted(keys, keys + m)
+        jump = torch.cat([torch.where(jump >= ends, jump.new_full((1,), n), jump), jump.new_full((1,), n)])
+        kept = torch.zeros(n + 1, dtype=torch.bool, device=hits.device)
+        kept[(last - counts)[counts > 0]] = True                        # every stream's first hit
+        for _ in range(int(counts.max().item()).bit_length()):
+            kept[jump[kept]] = True
+            jump = jump[jump]
+        kept = kept[:n]
+        before = torch.cat([last.new_zeros(1), torch.cumsum(kept, 0)])
+        return hits[kept], before[last] - before[last - counts]
+
     def frame_decode_chunks(self, framed: torch.Tensor, chunk_type, body_off, body_len, chunk_crc, out, out_off, out_cap):
         self._bind()
         nc = body_len.numel()

@@ -5,7 +5,8 @@
                                             # libsnappier_hip_frame_index.so, libsnappier_hip_frame_chunked.so, libsnappier_hip_frame_update.so,
                                             # libsnappier_hip_frame_append.so, libsnappier_hip_frame_splice.so, libsnappier_hip_frame_rechunk.so,
                                             # libsnappier_hip_frame_compose.so, libsnappier_hip_frame_digest.so,
-                                            # libsnappier_hip_frame_diff.so, libsnappier_hip_frame_find.so
+                                            # libsnappier_hip_frame_diff.so, libsnappier_hip_frame_find.so,
+                                            # libsnappier_hip_frame_edit.so
                                             # (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
@@ -53,6 +54,8 @@ LIBS = {
     "libsnappier_hip_frame_diff.so": ["frame_diff.hip"],
     # include/snappier_hip_frame_find.h: device batch find (where a byte string occurs in decoded windows) of seekable framed streams, the windows' chunks decoded into scratch -- the same kind of extension
     "libsnappier_hip_frame_find.so": ["frame_find.hip"],
+    # include/snappier_hip_frame_edit.h: device batch edit (a sorted edit script per stream: many splices in one call) of seekable framed streams, with the new index -- the same kind of extension
+    "libsnappier_hip_frame_edit.so": ["frame_edit.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 # every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)
