@@ -26,6 +26,10 @@ RECHUNK_REWRITE_ALL = 1                  # SNP_RECHUNK_REWRITE_ALL (include/snap
 DIFF_PREFIX, DIFF_SUFFIX, DIFF_EXACT = 1, 2, 4   # SNP_DIFF_PREFIX, SNP_DIFF_SUFFIX, SNP_DIFF_EXACT (include/snappier_hip_frame_diff.h)
 FIND_MAX_NEEDLE = 256    # SNP_FIND_MAX_NEEDLE (include/snappier_hip_frame_find.h)
 FIND_TILE = 16384        # kFindTile (csrc/frame_find_device.h): the start positions one workgroup step of the find takes
+CUTS_MIN_WINDOW, CUTS_MAX_WINDOW = 32, 32767   # SNP_CUTS_MIN_WINDOW, SNP_CUTS_MAX_WINDOW (include/snappier_hip_frame_cuts.h)
+CUTS_TILE = 4096         # kCutsTile (csrc/frame_cuts_device.h): the positions one workgroup of the cut finder takes at a time -- its seam
+CUTS_BLOCK = 64          # kCutsBlock: the positions one stored hash maximum covers
+CUTS_RUN = 17            # kCutsRun: the positions one lane hashes in a row
 # snp_option (include/snappier_hip.h)
 (OPT_DECODE_LAYOUT, OPT_SMALL_BLOCK_MAX, OPT_SMALL_BLOCK_MIN_BATCH, OPT_COMPRESS_LAYOUT, OPT_COMPRESS_WINDOW_MAX_BATCH,
  OPT_TABLE_PROBE_TRIES, OPT_TABLE_PROBE_MAX_BYTES, OPT_PARALLEL_DECODE_MIN, OPT_FENCED, OPT_DECODE_LEFTOVERS, OPT_CRC_KERNEL,
@@ -223,6 +227,13 @@ _EXTENSIONS = {
         "snp_frame_edit_indexed_workspace": (_u64, [_u32, _u32, _u32, _u64, _u32]),
         "snp_frame_edit_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32,
                                                 _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device content-defined chunking: the cuts the bytes of every buffer define, and the chunked frame encode with the pieces given by the caller
+    "frame_cuts": ("libsnappier_hip_frame_cuts.so", "snappier_hip_frame_cuts.h", {
+        "snp_content_cuts_workspace": (_u64, [_u32, _u64, _u32]),
+        "snp_content_cuts_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+        "snp_frame_encode_cuts_workspace": (_u64, [_u32, _u32, _u64]),
+        "snp_frame_encode_cuts_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -273,6 +284,7 @@ FRAME_DIGEST_PATH = _extension_path("frame_digest")
 FRAME_DIFF_PATH = _extension_path("frame_diff")
 FRAME_FIND_PATH = _extension_path("frame_find")
 FRAME_EDIT_PATH = _extension_path("frame_edit")
+FRAME_CUTS_PATH = _extension_path("frame_cuts")
 
 
 def buffers_lib() -> C.CDLL:
@@ -355,6 +367,11 @@ def frame_edit_lib() -> C.CDLL:
     return _extension("frame_edit")
 
 
+def frame_cuts_lib() -> C.CDLL:
+    """libsnappier_hip_frame_cuts.so (include/snappier_hip_frame_cuts.h)."""
+    return _extension("frame_cuts")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -417,6 +434,10 @@ def frame_find_declared_symbols() -> list[str]:
 
 def frame_edit_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_edit"))
+
+
+def frame_cuts_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_cuts"))
 
 
 def status_string(st: int) -> str:

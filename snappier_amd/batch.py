@@ -305,6 +305,123 @@ class BlockCodec:
         raise_for_status(st, self.ctx.handle)
         return out, out_off, out_len, status, result, index
 
+    # -- content-defined chunking (libsnappier_hip_frame_cuts.so) ------------------------------------------------------------------------------
+    @staticmethod
+    def _check_cut_params(method: str, window: int, max_bytes: int):
+        if not (N.CUTS_MIN_WINDOW <= window <= N.CUTS_MAX_WINDOW and window < max_bytes <= N.BLOCK_SIZE):
+            raise ValueError(f"{method}: window = {window}, max_bytes = {max_bytes}; window must be {N.CUTS_MIN_WINDOW} .. {N.CUTS_MAX_WINDOW} "
+                             f"and window < max_bytes <= {N.BLOCK_SIZE}")
+
+    def content_cuts(self, data: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, window: int = 2048, max_bytes: int = 16384,
+                     max_cuts: int | None = None, work: torch.Tensor | None = None, span_bytes: int | None = None):
+        """Where the bytes of every buffer put its cuts (snp_content_cuts_batch, libsnappier_hip_frame_cuts.so):
+        -> (cut_first, cuts, status, result).
+
+        Buffer b is data[in_off[b] .. +in_len[b]) (int64).  Offset c of a buffer is a content cut when the gear hash of the 32 bytes before
+        it is larger than that of the `window` offsets before c and no smaller than that of the `window` offsets behind it; pieces longer
+        than max_bytes are cut again every max_bytes (include/snappier_hip_frame_cuts.h has the rule).  The mean piece is about 2 * window
+        bytes, and an insert or delete moves the cuts behind it along with the bytes.  cuts[cut_first[b] .. cut_first[b + 1]) (int64) are
+        buffer b's cuts, ascending, relative to its first byte; result is the 4-element int64 d_result: [0] = cuts the batch needs,
+        [1] = cuts written, [2] = bytes the batch holds, [3] = buffers that are OK.  Defaults: max_cuts = the sum over the buffers of
+        in_len / (window + 1) + in_len / max_bytes, which no buffer exceeds, and span_bytes = the sum of in_len -- ONE synchronising
+        read-back for the two sums; a caller that passes max_cuts, span_bytes and work enqueues only."""
+        self._check_cut_params("content_cuts", window, max_bytes)
+        self._bind()
+        nb = in_len.numel()
+        if max_cuts is None or span_bytes is None:
+            n = in_len.to(torch.int64)
+            sums = torch.stack([(n // (window + 1) + n // max_bytes).sum(), n.sum()]).tolist() if nb else [0, 0]
+            max_cuts = int(sums[0]) if max_cuts is None else max_cuts
+            span_bytes = int(sums[1]) if span_bytes is None else span_bytes
+        CL = N.frame_cuts_lib()
+        work = self._work("content_cuts", work, CL.snp_content_cuts_workspace, nb, span_bytes, window)
+        data = self._readable(data, nb)
+        cut_first = torch.zeros(nb + 1, dtype=torch.int64, device=self.device)
+        cuts = torch.empty(max(max_cuts, 1), dtype=torch.int64, device=self.device)
+        status = torch.empty(nb, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        st = CL.snp_content_cuts_batch(self.ctx.handle, _p(data), _p(in_off), _p(in_len), nb, window, max_bytes, span_bytes, max_cuts,
+                                       _p(cut_first), _p(cuts), _p(status), _p(work), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return cut_first, cuts[:max_cuts], status, result
+
+    def frame_encode_at_cuts(self, data: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, cut_first: torch.Tensor, cuts: torch.Tensor,
+                             with_index: bool = True, out: torch.Tensor | None = None, out_off: torch.Tensor | None = None,
+                             out_cap: torch.Tensor | None = None, max_chunks: int | None = None, stage_cap: int | None = None,
+                             work: torch.Tensor | None = None):
+        """frame_encode_seekable with the pieces given by the caller (snp_frame_encode_cuts_batch, libsnappier_hip_frame_cuts.so):
+        -> (out, out_off, out_len, status, result, FrameIndex | None), as frame_encode_seekable returns them.
+
+        Buffer b's chunks are the pieces between cuts[cut_first[b] .. cut_first[b + 1]) (int64, ascending, inside (0, in_len[b]), relative
+        to the buffer's first byte; no piece longer than 65536) -- the cuts of content_cuts, the positions of a delimiter from the find, or
+        k * chunk_bytes, where every output is frame_encode_seekable's.  A buffer with a bad list gets status BAD_ARG alone.  Defaults:
+        max_chunks = cuts.numel() + the buffers, out_cap = 10 + 8 * (the buffer's cuts + 1) + n per buffer (from cut_first, on the
+        device), stage_cap = bytes + bytes / 6 + 69 * max_chunks, the documented bound; a default out costs ONE synchronising read-back,
+        and so does a default stage_cap.  A caller that passes out, out_off, out_cap, max_chunks, stage_cap and work enqueues only."""
+        self._bind()
+        nb = in_len.numel()
+        n = in_len.to(torch.int64)
+        ncuts = cuts.numel()
+        if max_chunks is None:
+            max_chunks = ncuts + nb
+        if out_cap is None:
+            out_cap = 10 + 8 * ((cut_first[1:] - cut_first[:-1]).clamp(0, ncuts) + 1) + n
+        if out_off is None:
+            out_off = torch.cumsum(out_cap, 0) - out_cap
+        if out is None or stage_cap is None:
+            sums = torch.stack([(out_off + out_cap).max(), n.sum()]).tolist() if nb else [0, 0]
+            if out is None:
+                out = torch.empty(max(int(sums[0]), 1), dtype=torch.uint8, device=self.device)
+            if stage_cap is None:
+                stage_cap = int(sums[1]) + int(sums[1]) // 6 + 69 * max_chunks
+        CL = N.frame_cuts_lib()
+        work = self._work("frame_encode_at_cuts", work, CL.snp_frame_encode_cuts_workspace, nb, max_chunks, stage_cap)
+        data = self._readable(data, nb)
+        out_len = torch.empty(nb, dtype=torch.int64, device=self.device)
+        status = torch.empty(nb, dtype=torch.int32, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)
+        index, ix = None, [None] * 5
+        if with_index:
+            first = torch.zeros(nb + 1, dtype=torch.int64, device=self.device)
+            start = torch.empty(max(max_chunks, 1), dtype=torch.int64, device=self.device)
+            pos = torch.empty(max(max_chunks, 1), dtype=torch.int64, device=self.device)
+            total = torch.empty(max(nb, 1), dtype=torch.int64, device=self.device)
+            tail = torch.empty(max(nb, 1), dtype=torch.int32, device=self.device)
+            ix = [first, start, pos, total, tail]
+            index = FrameIndex(first, start[:max_chunks], pos[:max_chunks], total[:nb], tail[:nb], result)
+        st = CL.snp_frame_encode_cuts_batch(self.ctx.handle, _p(data), _p(in_off), _p(in_len), nb, _p(cut_first), _p(cuts), ncuts, max_chunks,
+                                            stage_cap, _p(out), _p(out_off), _p(out_cap), _p(out_len), _p(status), *[_p(t) for t in ix], _p(work),
+                                            _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return out, out_off, out_len, status, result, index
+
+    def frame_encode_content_defined(self, data: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, window: int = 2048,
+                                     max_bytes: int = 16384, with_index: bool = True, out: torch.Tensor | None = None,
+                                     out_off: torch.Tensor | None = None, out_cap: torch.Tensor | None = None):
+        """Seekable framed streams whose chunks follow the content: content_cuts and frame_encode_at_cuts back to back on the stream, with no
+        read-back between them -> (out, out_off, out_len, status, result, FrameIndex | None), as frame_encode_seekable returns them.
+
+        Everything is sized by the documented bounds, from ONE synchronising read-back of the batch's sums in front: per buffer
+        in_len / (window + 1) + in_len / max_bytes cuts, one chunk more than cuts, 10 + 8 * chunks + n bytes of output.  Two versions of
+        a buffer that differ by an insert or a delete, each encoded here from scratch, hold the same chunks outside the neighbourhood of the
+        edit, so frame_diff_streams skips them by header CRC in both directions."""
+        self._check_cut_params("frame_encode_content_defined", window, max_bytes)
+        nb = in_len.numel()
+        n = in_len.to(torch.int64)
+        bound = n // (window + 1) + n // max_bytes                      # cuts per buffer, at the most
+        if out_cap is None:
+            out_cap = 10 + 8 * (bound + 1) + n
+        if out_off is None:
+            out_off = torch.cumsum(out_cap, 0) - out_cap
+        sums = torch.stack([bound.sum(), n.sum(), (out_off + out_cap).max()]).tolist() if nb else [0, 0, 0]
+        max_cuts, nbytes = int(sums[0]), int(sums[1])
+        if out is None:
+            out = torch.empty(max(int(sums[2]), 1), dtype=torch.uint8, device=self.device)
+        cut_first, cuts, _, _ = self.content_cuts(data, in_off, in_len, window, max_bytes, max_cuts=max_cuts, span_bytes=nbytes)
+        max_chunks = max_cuts + nb
+        return self.frame_encode_at_cuts(data, in_off, in_len, cut_first, cuts, with_index, out, out_off, out_cap, max_chunks,
+                                         nbytes + nbytes // 6 + 69 * max_chunks)
+
     def frame_decode_buffers(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, out: torch.Tensor, out_off: torch.Tensor,
                              out_cap: torch.Tensor, max_chunks: int | None = None, max_spans: int | None = None, work: torch.Tensor | None = None):
         """Many framed streams in one call (snp_frame_decode_buffers_batch, libsnappier_hip_frame_buffers.so): -> (out_len, status, result).

@@ -6,7 +6,7 @@
                                             # libsnappier_hip_frame_append.so, libsnappier_hip_frame_splice.so, libsnappier_hip_frame_rechunk.so,
                                             # libsnappier_hip_frame_compose.so, libsnappier_hip_frame_digest.so,
                                             # libsnappier_hip_frame_diff.so, libsnappier_hip_frame_find.so,
-                                            # libsnappier_hip_frame_edit.so
+                                            # libsnappier_hip_frame_edit.so, libsnappier_hip_frame_cuts.so
                                             # (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
@@ -56,6 +56,8 @@ LIBS = {
     "libsnappier_hip_frame_find.so": ["frame_find.hip"],
     # include/snappier_hip_frame_edit.h: device batch edit (a sorted edit script per stream: many splices in one call) of seekable framed streams, with the new index -- the same kind of extension
     "libsnappier_hip_frame_edit.so": ["frame_edit.hip"],
+    # include/snappier_hip_frame_cuts.h: device content-defined chunking -- the cuts the bytes of every buffer define, and the chunked frame encode with the pieces given by the caller -- the same kind of extension
+    "libsnappier_hip_frame_cuts.so": ["frame_cuts.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 # every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)
