@@ -30,6 +30,7 @@ CUTS_MIN_WINDOW, CUTS_MAX_WINDOW = 32, 32767   # SNP_CUTS_MIN_WINDOW, SNP_CUTS_M
 CUTS_TILE = 4096         # kCutsTile (csrc/frame_cuts_device.h): the positions one workgroup of the cut finder takes at a time -- its seam
 CUTS_BLOCK = 64          # kCutsBlock: the positions one stored hash maximum covers
 CUTS_RUN = 17            # kCutsRun: the positions one lane hashes in a row
+DEDUP_NONE = (1 << 64) - 1   # SNP_DEDUP_NONE (include/snappier_hip_frame_dedup.h): canon of a row that takes no part (-1 in an int64 tensor)
 # snp_option (include/snappier_hip.h)
 (OPT_DECODE_LAYOUT, OPT_SMALL_BLOCK_MAX, OPT_SMALL_BLOCK_MIN_BATCH, OPT_COMPRESS_LAYOUT, OPT_COMPRESS_WINDOW_MAX_BATCH,
  OPT_TABLE_PROBE_TRIES, OPT_TABLE_PROBE_MAX_BYTES, OPT_PARALLEL_DECODE_MIN, OPT_FENCED, OPT_DECODE_LEFTOVERS, OPT_CRC_KERNEL,
@@ -234,6 +235,11 @@ _EXTENSIONS = {
         "snp_frame_encode_cuts_workspace": (_u64, [_u32, _u32, _u64]),
         "snp_frame_encode_cuts_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp])}),
+    # device batch dedup of seekable framed streams by chunk: the pack, its index and the compose recipes
+    "frame_dedup": ("libsnappier_hip_frame_dedup.so", "snappier_hip_frame_dedup.h", {
+        "snp_frame_dedup_indexed_workspace": (_u64, [_u32, _u64]),
+        "snp_frame_dedup_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -285,6 +291,7 @@ FRAME_DIFF_PATH = _extension_path("frame_diff")
 FRAME_FIND_PATH = _extension_path("frame_find")
 FRAME_EDIT_PATH = _extension_path("frame_edit")
 FRAME_CUTS_PATH = _extension_path("frame_cuts")
+FRAME_DEDUP_PATH = _extension_path("frame_dedup")
 
 
 def buffers_lib() -> C.CDLL:
@@ -372,6 +379,11 @@ def frame_cuts_lib() -> C.CDLL:
     return _extension("frame_cuts")
 
 
+def frame_dedup_lib() -> C.CDLL:
+    """libsnappier_hip_frame_dedup.so (include/snappier_hip_frame_dedup.h)."""
+    return _extension("frame_dedup")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -438,6 +450,10 @@ def frame_edit_declared_symbols() -> list[str]:
 
 def frame_cuts_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_cuts"))
+
+
+def frame_dedup_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_dedup"))
 
 
 def status_string(st: int) -> str:

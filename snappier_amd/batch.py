@@ -1029,6 +1029,87 @@ class BlockCodec:
                                                                    need[4], seg_first, seg_stream, seg_off, seg_len)
         return out[:need[-1]], out_off, out_len, status, new_index
 
+    # -- dedup by chunk (libsnappier_hip_frame_dedup.so) -----------------------------------------------------------------------------------------
+    def frame_dedup_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", nbase: int,
+                            max_entries: int, max_segs: int, out: torch.Tensor | None, work: torch.Tensor | None = None):
+        """The duplicate chunks of a batch of seekable framed streams, the unique ones of the new streams once (snp_frame_dedup_indexed_batch,
+        libsnappier_hip_frame_dedup.so): -> (out_len, status, canon, FrameIndex of the pack, recipe, result).  The direct call: it enqueues
+        only (it allocates its outputs, and the workspace when `work` is None).
+
+        The first nbase streams are the base (stored already, earlier packs for example), the others are new.  canon (int64, one per index
+        row) maps every row to the lowest row whose chunk is byte-identical, to itself when there is none, and to DEDUP_NONE (-1 as int64)
+        for a row of length 0 or of a stream that failed.  The pack goes to `out` (its capacity is out.numel(); None: 0): the identifier and
+        the unique chunks of the admitted new streams, verbatim, with out_len (int64, 1 value) and its own FrameIndex (start / pos hold
+        max_entries rows).  recipe = (seg_first, seg_stream, seg_off, seg_len) is the segment list frame_compose_indexed takes, over the
+        sources base stream s -> s, the pack -> nbase (frame_restore_to_memory).  status (int32) is per stream.  result is the 8-element
+        int64 d_result: [0] = unique rows, [1] = pack bytes, [2] = segments needed, [3] = streams OK, [4] = rows that take part, [5] = rows
+        merged, [6] = rows with a leader's key but other bytes, [7] = chunk bytes saved; max_entries = max_segs = 0 with no `out` is the
+        sizing call (include/snappier_hip_frame_dedup.h)."""
+        self._bind()
+        ns, ne = in_len.numel(), index.nentries
+        if not 0 <= nbase <= ns:
+            raise ValueError(f"frame_dedup_indexed: nbase = {nbase}, the batch holds {ns} streams")
+        DL = N.frame_dedup_lib()
+        framed = self._readable(framed, ns)
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+        out_cap = out.numel() if out is not None else 0
+        dev = self.device
+        out_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        status = torch.zeros(ns, dtype=torch.int32, device=dev)
+        canon = torch.empty(max(ne, 1), dtype=torch.int64, device=dev)
+        pk = [torch.zeros(2, dtype=torch.int64, device=dev), torch.empty(max(max_entries, 1), dtype=torch.int64, device=dev),
+              torch.empty(max(max_entries, 1), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+              torch.zeros(1, dtype=torch.int32, device=dev)]
+        seg_first = torch.zeros(ns - nbase + 1, dtype=torch.int64, device=dev)
+        seg_stream = torch.zeros(max(max_segs, 1), dtype=torch.int32, device=dev)
+        seg_off = torch.zeros(max(max_segs, 1), dtype=torch.int64, device=dev)
+        seg_len = torch.zeros(max(max_segs, 1), dtype=torch.int64, device=dev)
+        result = torch.empty(8, dtype=torch.int64, device=dev)
+        w = self._work("frame_dedup_indexed", work, DL.snp_frame_dedup_indexed_workspace, ns, ne)
+        st = DL.snp_frame_dedup_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                              _p(index.total), _p(index.tail), ne, nbase, max_entries, max_segs, out_cap, _p(out), _p(out_len),
+                                              _p(status), _p(canon), *[_p(t) for t in pk], _p(seg_first), _p(seg_stream), _p(seg_off), _p(seg_len),
+                                              _p(w), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        pack_index = FrameIndex(pk[0], pk[1][:max_entries], pk[2][:max_entries], pk[3], pk[4], result)
+        return out_len, status, canon[:ne], pack_index, (seg_first, seg_stream[:max_segs], seg_off[:max_segs], seg_len[:max_segs]), result
+
+    def frame_dedup_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", nbase: int = 0):
+        """Dedup a batch of seekable framed streams by chunk: -> (pack, FrameIndex of the pack, recipe, canon, status, result).
+
+        ONE sizing call, ONE synchronising read of its result, the pack, its index and the recipe arrays allocated to exactly what the
+        batch needs, then the call.  The pack is a framed stream: it goes into every seekable call with its index, and into the next
+        frame_dedup_to_memory as a base stream; frame_restore_to_memory rebuilds the new streams from the base streams, the pack and the
+        recipe."""
+        *_, result = self.frame_dedup_indexed(framed, in_off, in_len, index, nbase, 0, 0, None)
+        need = result.tolist()
+        if need[0] > 0xFFFFFFFF or need[2] > 0xFFFFFFFF:
+            raise ValueError(f"frame_dedup_to_memory: {need[0]} unique rows and {need[2]} segments, one call takes 2^32 - 1 of each")
+        out = torch.empty(max(need[1], 10), dtype=torch.uint8, device=self.device)
+        _, status, canon, pack_index, recipe, result = self.frame_dedup_indexed(framed, in_off, in_len, index, nbase, need[0], need[2], out)
+        return out[:need[1]], pack_index, recipe, canon, status, result
+
+    def frame_restore_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", nbase: int,
+                                pack: torch.Tensor, pack_index: "FrameIndex", recipe, chunk_bytes: int = N.BLOCK_SIZE, align: int = 1,
+                                max_bytes: int | None = None):
+        """The new streams of a dedup again (frame_compose_to_memory on a recipe): -> (out, out_off, out_len, status, FrameIndex).
+
+        The sources are the first nbase streams of (framed, in_off, in_len, index) and the pack with its index, as source nbase.  With base
+        streams the pack is copied once behind `framed` (one torch.cat: the compose call takes one tensor); with nbase = 0 the pack alone is
+        the source.  Every chunk is copied as it is, so a stream that was the identifier plus non-empty data chunks comes back byte for
+        byte.  ONE synchronising read for the base streams' row count when nbase > 0, besides those of frame_compose_to_memory."""
+        dev = self.device
+        rows = min(int(index.first[nbase]), index.nentries) if nbase else 0
+        src = torch.cat([framed, pack]) if nbase else pack
+        pack_off = torch.tensor([framed.numel() if nbase else 0], dtype=torch.int64, device=dev)
+        pack_len = torch.tensor([pack.numel()], dtype=torch.int64, device=dev)
+        first = torch.cat([index.first[:nbase], index.first.new_full((1,), rows), pack_index.first[1:2] + rows])
+        sources = FrameIndex(first, torch.cat([index.start[:rows], pack_index.start]), torch.cat([index.pos[:rows], pack_index.pos]),
+                             torch.cat([index.total[:nbase], pack_index.total]), torch.cat([index.tail[:nbase], pack_index.tail]))
+        return self.frame_compose_to_memory(src, torch.cat([in_off[:nbase].to(torch.int64), pack_off]),
+                                            torch.cat([in_len[:nbase].to(torch.int64), pack_len]), sources, *recipe, chunk_bytes=chunk_bytes,
+                                            align=align, max_bytes=max_bytes)
+
     def frame_digest_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", req_stream: torch.Tensor,
                              req_off: torch.Tensor, req_len: torch.Tensor, edge_cap: int | None = None, work: torch.Tensor | None = None):
         """The CRC-32C of any number of windows of what framed streams decode to, from the CRCs their chunk headers carry, with no decode of

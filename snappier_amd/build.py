@@ -6,7 +6,8 @@
                                             # libsnappier_hip_frame_append.so, libsnappier_hip_frame_splice.so, libsnappier_hip_frame_rechunk.so,
                                             # libsnappier_hip_frame_compose.so, libsnappier_hip_frame_digest.so,
                                             # libsnappier_hip_frame_diff.so, libsnappier_hip_frame_find.so,
-                                            # libsnappier_hip_frame_edit.so, libsnappier_hip_frame_cuts.so
+                                            # libsnappier_hip_frame_edit.so, libsnappier_hip_frame_cuts.so,
+                                            # libsnappier_hip_frame_dedup.so
                                             # (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
@@ -58,6 +59,8 @@ LIBS = {
     "libsnappier_hip_frame_edit.so": ["frame_edit.hip"],
     # include/snappier_hip_frame_cuts.h: device content-defined chunking -- the cuts the bytes of every buffer define, and the chunked frame encode with the pieces given by the caller -- the same kind of extension
     "libsnappier_hip_frame_cuts.so": ["frame_cuts.hip"],
+    # include/snappier_hip_frame_dedup.h: device batch dedup of seekable framed streams by chunk -- the unique chunks of the new streams once, as a pack with its index, and the compose recipes that rebuild every stream -- the same kind of extension
+    "libsnappier_hip_frame_dedup.so": ["frame_dedup.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 # every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)

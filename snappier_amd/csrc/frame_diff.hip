@@ -23,6 +23,7 @@
 #include "scan_tiles.h"
 #include "frame_edges_device.h"
 #include "frame_diff_device.h"
+#include "bytes16_device.h"
 #include "../../include/snappier_hip_frame_diff.h"
 
 namespace {
@@ -266,15 +267,6 @@ __global__ __launch_bounds__(256) void k_df_fail(DfWork w, u32 nrows)
     const u32 r = c.tag[t];
     if (r == kNone || c.status[t] == SNP_OK) return;
     atomic_min64(w.fail[side] + r, fail_key(c.body_off[t], c.status[t]));
-}
-
-// the first of 16 bytes (in the direction) at which two words differ, 16 if none
-__device__ __forceinline__ u32 first_diff16(const snp_u128_unaligned& x, const snp_u128_unaligned& y, u32 dir)
-{
-    const u64 lo = (x.v[0] ^ y.v[0]) | static_cast<u64>(x.v[1] ^ y.v[1]) << 32, hi = (x.v[2] ^ y.v[2]) | static_cast<u64>(x.v[3] ^ y.v[3]) << 32;
-    if (!(lo | hi)) return 16;
-    if (!dir) return lo ? static_cast<u32>(__builtin_ctzll(lo)) >> 3 : 8u + (static_cast<u32>(__builtin_ctzll(hi)) >> 3);
-    return hi ? static_cast<u32>(__builtin_clzll(hi)) >> 3 : 8u + (static_cast<u32>(__builtin_clzll(lo)) >> 3);
 }
 
 // Workgroups stride over (piece, slice); a slice takes every `slices`-th block of kCompareBlock bytes of the piece, counted in the direction,
