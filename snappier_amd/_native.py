@@ -30,6 +30,7 @@ CUTS_MIN_WINDOW, CUTS_MAX_WINDOW = 32, 32767   # SNP_CUTS_MIN_WINDOW, SNP_CUTS_M
 CUTS_TILE = 4096         # kCutsTile (csrc/frame_cuts_device.h): the positions one workgroup of the cut finder takes at a time -- its seam
 CUTS_BLOCK = 64          # kCutsBlock: the positions one stored hash maximum covers
 CUTS_RUN = 17            # kCutsRun: the positions one lane hashes in a row
+RECUT_REWRITE_ALL = 1                    # SNP_RECUT_REWRITE_ALL (include/snappier_hip_frame_recut.h)
 DEDUP_NONE = (1 << 64) - 1   # SNP_DEDUP_NONE (include/snappier_hip_frame_dedup.h): canon of a row that takes no part (-1 in an int64 tensor)
 # snp_option (include/snappier_hip.h)
 (OPT_DECODE_LAYOUT, OPT_SMALL_BLOCK_MAX, OPT_SMALL_BLOCK_MIN_BATCH, OPT_COMPRESS_LAYOUT, OPT_COMPRESS_WINDOW_MAX_BATCH,
@@ -240,6 +241,11 @@ _EXTENSIONS = {
         "snp_frame_dedup_indexed_workspace": (_u64, [_u32, _u64]),
         "snp_frame_dedup_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp,
                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch recut of seekable framed streams to a caller's cut list: clean chunks copied, the other pieces decoded and compressed again, the new index
+    "frame_recut": ("libsnappier_hip_frame_recut.so", "snappier_hip_frame_recut.h", {
+        "snp_frame_recut_indexed_workspace": (_u64, [_u32, _u32, _u64, _u32]),
+        "snp_frame_recut_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u32, _u64, _u32,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -292,6 +298,7 @@ FRAME_FIND_PATH = _extension_path("frame_find")
 FRAME_EDIT_PATH = _extension_path("frame_edit")
 FRAME_CUTS_PATH = _extension_path("frame_cuts")
 FRAME_DEDUP_PATH = _extension_path("frame_dedup")
+FRAME_RECUT_PATH = _extension_path("frame_recut")
 
 
 def buffers_lib() -> C.CDLL:
@@ -384,6 +391,11 @@ def frame_dedup_lib() -> C.CDLL:
     return _extension("frame_dedup")
 
 
+def frame_recut_lib() -> C.CDLL:
+    """libsnappier_hip_frame_recut.so (include/snappier_hip_frame_recut.h)."""
+    return _extension("frame_recut")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -454,6 +466,10 @@ def frame_cuts_declared_symbols() -> list[str]:
 
 def frame_dedup_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_dedup"))
+
+
+def frame_recut_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_recut"))
 
 
 def status_string(st: int) -> str:

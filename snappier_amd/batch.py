@@ -956,6 +956,107 @@ class BlockCodec:
                                                                    need[4], rewrite_all)
         return out[:need[-1]], out_off, out_len, status, new_index
 
+    # -- recut: rechunk to a caller's cut list (libsnappier_hip_frame_recut.so) ------------------------------------------------------------------
+    def frame_recut_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", cut_first: torch.Tensor,
+                            cuts: torch.Tensor, out: torch.Tensor, out_off: torch.Tensor, out_cap: torch.Tensor, max_slots: int, stage_cap: int,
+                            max_entries: int, rewrite_all: bool = False, work: torch.Tensor | None = None, with_bound: bool = False):
+        """Framed streams brought to the pieces of a cut list through their chunk index (snp_frame_recut_indexed_batch,
+        libsnappier_hip_frame_recut.so): -> (out_len, status, FrameIndex, result) and, with_bound, out_bound behind them, as
+        frame_rechunk_indexed returns them.  The direct call: it enqueues only (it allocates its outputs, and the workspace when `work` is None).
+
+        Stream b's pieces lie between cuts[cut_first[b] .. cut_first[b + 1]) (int64, ascending, inside (0, index.total[b]), relative to the
+        stream's first decoded byte; no piece longer than 65536) -- what content_cuts gives for the decoded bytes, record boundaries, or a grid.
+        The new stream of b goes to out[out_off[b] .. +out_cap[b]) and is what frame_encode_at_cuts writes for the stream's decoded bytes and
+        that list: an old chunk that already is a piece of it is copied, the other pieces are decoded and compressed again; skippable, padding
+        and repeated-identifier chunks are dropped.  rewrite_all decodes, verifies and compresses every chunk.  A stream whose chunks are the
+        list's pieces already is left alone (SNP_OK, out_len[b] = 0, its old rows), a stream with a bad list gets BAD_ARG alone, and a stream
+        is recut whole or not at all (include/snappier_hip_frame_recut.h).  stage_cap is ONE budget for the decoded and the compressed staging;
+        2 * dbytes + dbytes / 6 + 69 * rebuilt always holds it.  result is the 8-element int64 d_result: [0] = decode rows / chunk slots needed,
+        [1] = sum of out_len, [2] = staging bytes needed, [3] = streams written, [4] = rows of the new index needed, [5] = streams left alone,
+        [6] = chunks copied, [7] = pieces rebuilt; max_slots = stage_cap = 0 is the sizing call."""
+        self._bind()
+        ns = in_len.numel()
+        RL = N.frame_recut_lib()
+        framed, out = self._readable(framed, ns), self._readable(out, ns)
+        ne, ncuts = index.nentries, cuts.numel()
+        start, pos, cuts = self._readable(index.start, ns), self._readable(index.pos, ns), self._readable(cuts, ns)
+        out_len = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        status = torch.zeros(ns, dtype=torch.int32, device=self.device)
+        first = torch.zeros(ns + 1, dtype=torch.int64, device=self.device)
+        new_start = torch.empty(max(max_entries, 1), dtype=torch.int64, device=self.device)
+        new_pos = torch.empty(max(max_entries, 1), dtype=torch.int64, device=self.device)
+        total = torch.empty(ns, dtype=torch.int64, device=self.device)
+        tail = torch.empty(ns, dtype=torch.int32, device=self.device)
+        bound = torch.zeros(ns, dtype=torch.int64, device=self.device) if with_bound else None
+        result = torch.empty(8, dtype=torch.int64, device=self.device)
+        w = self._work("frame_recut_indexed", work, RL.snp_frame_recut_indexed_workspace, ns, max_slots, stage_cap, max_entries)
+        st = RL.snp_frame_recut_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                              _p(index.total), _p(index.tail), ne, _p(cut_first), _p(cuts), ncuts,
+                                              N.RECUT_REWRITE_ALL if rewrite_all else 0, max_slots, stage_cap, max_entries, _p(out), _p(out_off),
+                                              _p(out_cap), _p(out_len), _p(status), _p(first), _p(new_start), _p(new_pos), _p(total), _p(tail),
+                                              _p(bound), _p(w), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        got = (out_len, status, FrameIndex(first, new_start[:max_entries], new_pos[:max_entries], total, tail, result), result)
+        return got + (bound,) if with_bound else got
+
+    def frame_recut_to_memory(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", cut_first: torch.Tensor,
+                              cuts: torch.Tensor, rewrite_all: bool = False, align: int = 1, max_bytes: int | None = None):
+        """Recut framed streams given the framed tensor, its table, its index and the cut list: -> (out, out_off, out_len, status, FrameIndex).
+
+        ONE sizing call (max_slots = stage_cap = max_entries = 0, every out_cap 0) that also asks for each stream's size bound, ONE synchronising
+        read of its result and of the arena size (ValueError if that is above max_bytes), an arena in which stream b's slot is its bound rounded
+        up to `align` (0 for a stream that is left alone or refused), then the recut with exactly what the sizing call asked for.  Streams with
+        out_len 0 -- those whose chunks were the list's pieces already among them -- are not in the arena: the caller keeps their old bytes, and
+        the returned index holds their old rows."""
+        ns = in_len.numel()
+        zero = torch.zeros(ns, dtype=torch.int64, device=self.device)
+        empty = torch.empty(0, dtype=torch.uint8, device=self.device)
+        _, _, _, result, bound = self.frame_recut_indexed(framed, in_off, in_len, index, cut_first, cuts, empty, zero, zero, 0, 0, 0, rewrite_all,
+                                                          with_bound=True)
+        slot = (bound + (align - 1)) // align * align
+        ends = torch.cumsum(slot, 0)
+        out_off = ends - slot
+        need = torch.cat([result, ends[-1:] if ns else zero[:0].new_zeros(1)]).tolist()
+        if need[0] > 0xFFFFFFFF or need[4] > 0xFFFFFFFF:
+            raise ValueError(f"frame_recut_to_memory: {need[0]} chunk slots and {need[4]} index rows, one call takes 2^32 - 1 of each")
+        if max_bytes is not None and need[-1] > max_bytes:
+            raise ValueError(f"frame_recut_to_memory: the new streams take up to {need[-1]} bytes, max_bytes = {max_bytes}")
+        out = torch.empty(max(need[-1], 1), dtype=torch.uint8, device=self.device)
+        out_len, status, new_index, _ = self.frame_recut_indexed(framed, in_off, in_len, index, cut_first, cuts, out, out_off, bound, need[0],
+                                                                 need[2], need[4], rewrite_all)
+        return out[:need[-1]], out_off, out_len, status, new_index
+
+    def frame_recut_content_defined(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", window: int = 2048,
+                                    max_bytes: int = 16384, rewrite_all: bool = False, align: int = 1, max_out_bytes: int | None = None):
+        """Stored streams brought to the chunks frame_encode_content_defined would write for what they decode to:
+        -> (out, out_off, out_len, status, FrameIndex), as frame_recut_to_memory returns them.
+
+        Every stream is read whole with the indexed read into a TRANSIENT device tensor, content_cuts runs on it, and the recut takes the
+        finder's cut_first / cuts as they lie on the device.  After an append, a splice or an edit script of a content-defined stream the cuts
+        are in step again window + 32 bytes behind each edit, so almost every chunk is copied; a grid store is converted with every piece
+        rebuilt.  THE TRANSIENT IS THE BATCH'S DECODED SIZE (the sum of index.total): a caller short of memory goes in parts, a slice of the
+        streams at a time.  It is freed before the recut allocates its arena.  A stream that the read refuses (a corrupt chunk, an index
+        that does not hold) gets the read's status, is not written and keeps its old rows.  Synchronising reads: one for the sizes of the
+        transient and of the cut list, the read's sizing, the recut's sizing."""
+        self._check_cut_params("frame_recut_content_defined", window, max_bytes)
+        ns = in_len.numel()
+        total = index.total.to(torch.int64).clamp(min=0)
+        ends = torch.cumsum(total, 0)
+        d_off = ends - total
+        sums = torch.stack([ends[-1], (total // (window + 1) + total // max_bytes).sum()]).tolist() if ns else [0, 0]
+        decoded = torch.empty(max(int(sums[0]), 1), dtype=torch.uint8, device=self.device)
+        req_stream = torch.arange(ns, dtype=torch.int32, device=self.device)
+        d_len, d_status, _ = self.frame_read_indexed(framed, in_off, in_len, index, req_stream, torch.zeros_like(total), total, decoded, d_off, total)
+        cut_first, cuts, _, _ = self.content_cuts(decoded, d_off, d_len, window, max_bytes, max_cuts=int(sums[1]), span_bytes=int(sums[0]))
+        del decoded
+        # a stream the read refused goes in with the read's status as its tail: the recut hands that status back and leaves the stream alone
+        failed = d_status != 0
+        masked = FrameIndex(index.first, index.start, index.pos, index.total, torch.where(failed, d_status, index.tail), index.result)
+        out, out_off, out_len, status, new_index = self.frame_recut_to_memory(framed, in_off, in_len, masked, cut_first, cuts, rewrite_all, align,
+                                                                              max_out_bytes)
+        new_index.tail = torch.where(failed, index.tail, new_index.tail)
+        return out, out_off, out_len, torch.where(failed, d_status, status), new_index
+
     def frame_compose_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", chunk_bytes: int,
                               out: torch.Tensor, out_off: torch.Tensor, out_cap: torch.Tensor, max_slots: int, stage_cap: int, max_entries: int,
                               seg_first: torch.Tensor, seg_stream: torch.Tensor, seg_off: torch.Tensor, seg_len: torch.Tensor,

@@ -7,7 +7,7 @@
                                             # libsnappier_hip_frame_compose.so, libsnappier_hip_frame_digest.so,
                                             # libsnappier_hip_frame_diff.so, libsnappier_hip_frame_find.so,
                                             # libsnappier_hip_frame_edit.so, libsnappier_hip_frame_cuts.so,
-                                            # libsnappier_hip_frame_dedup.so
+                                            # libsnappier_hip_frame_dedup.so, libsnappier_hip_frame_recut.so
                                             # (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
@@ -61,6 +61,8 @@ LIBS = {
     "libsnappier_hip_frame_cuts.so": ["frame_cuts.hip"],
     # include/snappier_hip_frame_dedup.h: device batch dedup of seekable framed streams by chunk -- the unique chunks of the new streams once, as a pack with its index, and the compose recipes that rebuild every stream -- the same kind of extension
     "libsnappier_hip_frame_dedup.so": ["frame_dedup.hip"],
+    # include/snappier_hip_frame_recut.h: device batch recut of seekable framed streams to a caller's cut list -- the chunks that already are pieces copied, the others decoded and compressed again, with the new index -- the same kind of extension
+    "libsnappier_hip_frame_recut.so": ["frame_recut.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 # every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)

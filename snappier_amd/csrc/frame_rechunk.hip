@@ -137,19 +137,6 @@ __global__ __launch_bounds__(256) void k_rc_clear(u32 max_slots, ChunkRows rows,
     dstart[t] = 0;
 }
 
-// exclusive scan of v over the wavefront; *total: the sum
-__device__ __forceinline__ u64 wave_scan(u64 v, u64* total)
-{
-    const u32 lane = lane_id();
-    u64 inc = v;
-    for (u32 d = 1; d < 64; d <<= 1) {
-        const u64 o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    *total = __shfl(inc, 63, 64);
-    return inc - v;
-}
-
 // A workgroup per admitted stream walks its rows again, 256 at a time, with the dirty rows and their decoded bytes so far: dirty row j of the
 // stream is row adirty[b] + j of the table and decodes to the stream's staging bytes + the decoded bytes of the dirty rows before it.
 __global__ __launch_bounds__(256) void k_rc_fill(RcArgs a, RcStreams st, Admit admit, ChunkRows rows, u64* __restrict__ dstart)

@@ -136,6 +136,19 @@ struct RwOwners {
     u32 n;
 };
 
+// exclusive scan of v over the wavefront; *total: the sum (the fill kernels of the rechunk and the recut: a row's place among its stream's dirty rows)
+__device__ __forceinline__ u64 wave_scan(u64 v, u64* total)
+{
+    const u32 lane = lane_id();
+    u64 inc = v;
+    for (u32 d = 1; d < 64; d <<= 1) {
+        const u64 o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    *total = __shfl(inc, 63, 64);
+    return inc - v;
+}
+
 // the tail of the sizes kernels: what the wavefront's streams add to d_result[1] (bytes written), [3] (streams written) and [5] (the call's own
 // count), one atomic per wavefront each.  All lanes must call it.
 __device__ __forceinline__ void add_written(u64* result, u64 ok_len, u64 ok, u64 extra)
