@@ -31,6 +31,8 @@ CUTS_TILE = 4096         # kCutsTile (csrc/frame_cuts_device.h): the positions o
 CUTS_BLOCK = 64          # kCutsBlock: the positions one stored hash maximum covers
 CUTS_RUN = 17            # kCutsRun: the positions one lane hashes in a row
 RECUT_REWRITE_ALL = 1                    # SNP_RECUT_REWRITE_ALL (include/snappier_hip_frame_recut.h)
+VERIFY_NONE = (1 << 64) - 1  # SNP_VERIFY_NONE (include/snappier_hip_frame_verify.h): first_bad of a stream with no bad row (-1 in an int64 tensor)
+VERIFY_SKIPPED = -1          # SNP_VERIFY_SKIPPED: row_status of a row that was not looked at
 DEDUP_NONE = (1 << 64) - 1   # SNP_DEDUP_NONE (include/snappier_hip_frame_dedup.h): canon of a row that takes no part (-1 in an int64 tensor)
 # snp_option (include/snappier_hip.h)
 (OPT_DECODE_LAYOUT, OPT_SMALL_BLOCK_MAX, OPT_SMALL_BLOCK_MIN_BATCH, OPT_COMPRESS_LAYOUT, OPT_COMPRESS_WINDOW_MAX_BATCH,
@@ -246,6 +248,14 @@ _EXTENSIONS = {
         "snp_frame_recut_indexed_workspace": (_u64, [_u32, _u32, _u64, _u32]),
         "snp_frame_recut_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u32, _u64, _u32,
                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])}),
+    # device batch verify of seekable framed streams chunk by chunk in bounded scratch, and the repair planner: row verdicts to compose recipes over a replica
+    "frame_verify": ("libsnappier_hip_frame_verify.so", "snappier_hip_frame_verify.h", {
+        "snp_frame_verify_indexed_workspace": (_u64, [_u32, _u64, _u32, _u64]),
+        "snp_frame_verify_indexed_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp]),
+        "snp_frame_repair_plan_workspace": (_u64, [_u32]),
+        "snp_frame_repair_plan_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _vp])}),
 }
 _loaded: dict[str, C.CDLL] = {}
 
@@ -299,6 +309,7 @@ FRAME_EDIT_PATH = _extension_path("frame_edit")
 FRAME_CUTS_PATH = _extension_path("frame_cuts")
 FRAME_DEDUP_PATH = _extension_path("frame_dedup")
 FRAME_RECUT_PATH = _extension_path("frame_recut")
+FRAME_VERIFY_PATH = _extension_path("frame_verify")
 
 
 def buffers_lib() -> C.CDLL:
@@ -396,6 +407,11 @@ def frame_recut_lib() -> C.CDLL:
     return _extension("frame_recut")
 
 
+def frame_verify_lib() -> C.CDLL:
+    """libsnappier_hip_frame_verify.so (include/snappier_hip_frame_verify.h)."""
+    return _extension("frame_verify")
+
+
 def buffers_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("buffers"))
 
@@ -470,6 +486,10 @@ def frame_dedup_declared_symbols() -> list[str]:
 
 def frame_recut_declared_symbols() -> list[str]:
     return declared_symbols(_extension_header("frame_recut"))
+
+
+def frame_verify_declared_symbols() -> list[str]:
+    return declared_symbols(_extension_header("frame_verify"))
 
 
 def status_string(st: int) -> str:

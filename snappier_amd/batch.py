@@ -1211,6 +1211,116 @@ class BlockCodec:
                                             torch.cat([in_len[:nbase].to(torch.int64), pack_len]), sources, *recipe, chunk_bytes=chunk_bytes,
                                             align=align, max_bytes=max_bytes)
 
+    # -- verify and repair (libsnappier_hip_frame_verify.so) ----------------------------------------------------------------------------------------
+    def frame_verify_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex",
+                             slot_bytes: int | None = None, scratch_cap: int = 256 << 20, work: torch.Tensor | None = None):
+        """Which chunks of a batch of seekable framed streams are rotten (snp_frame_verify_indexed_batch, libsnappier_hip_frame_verify.so):
+        -> (row_status, status, nbad, first_bad, bad_bytes, flags, result).  Nothing is written but verdicts.
+
+        row_status (int32, one per index row) is what the framed decode gives that one chunk -- the decoder's status or ERR_CRC_MISMATCH --,
+        ERR_BAD_ARG for a row the index does not describe, ERR_OUTPUT_TOO_SMALL for a row longer than slot_bytes (not verified) and
+        VERIFY_SKIPPED for a row of a stream that was not looked at.  Per stream: status (int32: the stream's verdict, else its first bad
+        row's status), nbad, first_bad (a global row number; VERIFY_NONE, -1 as int64, when there is none), bad_bytes (int64) and flags
+        (int32; bit 0: the stream does not begin with the identifier).  Every data chunk is decoded and CRC-verified into scratch_cap bytes
+        inside the workspace, in rounds of scratch_cap // (slot_bytes rounded up to 16) rows; the results do not depend on scratch_cap.
+        result is the 8-element int64 d_result: [0] = rows looked at, [1] = rows not OK, [2] = decoded bytes verified, [3] = streams OK,
+        [4] = the longest checked row, [5] = rows left unverified, [6] = rounds, [7] = the sum of bad_bytes
+        (include/snappier_hip_frame_verify.h).  Default slot_bytes: a sizing call (scratch_cap = 0), then ONE synchronising read of its
+        d_result[4].  A caller that passes slot_bytes enqueues only (the outputs, and the workspace when `work` is None, are allocated)."""
+        self._bind()
+        ns, ne = in_len.numel(), index.nentries
+        VL = N.frame_verify_lib()
+        framed = self._readable(framed, ns)
+        start, pos = self._readable(index.start, ns), self._readable(index.pos, ns)
+        dev = self.device
+        row_status = torch.empty(max(ne, 1), dtype=torch.int32, device=dev)
+        status = torch.zeros(ns, dtype=torch.int32, device=dev)
+        nbad, first_bad, bad_bytes = (torch.zeros(ns, dtype=torch.int64, device=dev) for _ in range(3))
+        flags = torch.zeros(ns, dtype=torch.int32, device=dev)
+        result = torch.empty(8, dtype=torch.int64, device=dev)
+
+        def call(sb: int, cap: int, w: torch.Tensor | None):
+            w = self._work("frame_verify_indexed", w, VL.snp_frame_verify_indexed_workspace, ns, ne, sb, cap)
+            st = VL.snp_frame_verify_indexed_batch(self.ctx.handle, _p(framed), _p(in_off), _p(in_len), ns, _p(index.first), _p(start), _p(pos),
+                                                   _p(index.total), _p(index.tail), ne, sb, cap, _p(row_status), _p(status), _p(nbad),
+                                                   _p(first_bad), _p(bad_bytes), _p(flags), _p(w), _p(result))
+            raise_for_status(st, self.ctx.handle)
+
+        if slot_bytes is None:
+            call(N.BLOCK_SIZE, 0, None)
+            slot_bytes = min(max(result.tolist()[4], 1), N.BLOCK_SIZE)
+        if not 1 <= slot_bytes <= N.BLOCK_SIZE:
+            raise ValueError(f"frame_verify_indexed: slot_bytes = {slot_bytes}, must be 1 .. {N.BLOCK_SIZE}")
+        call(slot_bytes, scratch_cap, work)
+        return row_status[:ne], status, nbad, first_bad, bad_bytes, flags, result
+
+    def frame_repair_plan(self, index: "FrameIndex", row_status: torch.Tensor, rep_index: "FrameIndex", rp_stream: torch.Tensor,
+                          rp_replica: torch.Tensor, max_segs: int, work: torch.Tensor | None = None):
+        """The verdicts of frame_verify_indexed as compose recipes over a replica (snp_frame_repair_plan_batch): -> (plan_status, recipe,
+        result).  The direct call: it enqueues only.
+
+        Pair j names stream rp_stream[j] of `index` and replica rp_replica[j] of `rep_index` (int32 tensors).  Its output is the whole
+        stream: every run of rows whose row_status is OK one segment of the stream itself, every run of other rows one segment of the replica
+        over the same decoded range.  recipe = (seg_first, seg_stream, seg_off, seg_len) is the segment list frame_compose_indexed takes over
+        the sources stream s -> s, replica t -> nstreams + t.  plan_status (int32) is per pair: ERR_BAD_ARG for a pair out of range, a stream
+        or a replica whose index is not OK and totals that differ; ERR_OUTPUT_TOO_SMALL from the first pair whose segments pass max_segs.
+        result is the 4-element int64 d_result: [0] = segments needed, [1] = pairs planned, [2] = bytes taken from replicas, [3] = bytes
+        kept; max_segs = 0 is the sizing call."""
+        self._bind()
+        ns, ne, nrep, nout = index.total.numel(), min(index.start.numel(), row_status.numel()), rep_index.total.numel(), rp_stream.numel()
+        if rp_stream.dtype != torch.int32 or rp_replica.dtype != torch.int32 or rp_replica.numel() != nout:
+            raise ValueError("frame_repair_plan: rp_stream and rp_replica must be int32 tensors of one length")
+        VL = N.frame_verify_lib()
+        dev = self.device
+        start = self._readable(index.start, ns)
+        rows = self._readable(row_status, ns)
+        plan_status = torch.zeros(nout, dtype=torch.int32, device=dev)
+        seg_first = torch.zeros(nout + 1, dtype=torch.int64, device=dev)
+        seg_stream = torch.zeros(max(max_segs, 1), dtype=torch.int32, device=dev)
+        seg_off = torch.zeros(max(max_segs, 1), dtype=torch.int64, device=dev)
+        seg_len = torch.zeros(max(max_segs, 1), dtype=torch.int64, device=dev)
+        result = torch.empty(4, dtype=torch.int64, device=dev)
+        w = self._work("frame_repair_plan", work, VL.snp_frame_repair_plan_workspace, nout)
+        st = VL.snp_frame_repair_plan_batch(self.ctx.handle, _p(index.first), _p(start), _p(index.total), _p(index.tail), ne, ns, _p(rows),
+                                            _p(rep_index.total), _p(rep_index.tail), nrep, _p(rp_stream), _p(rp_replica), nout, max_segs,
+                                            _p(seg_first), _p(seg_stream), _p(seg_off), _p(seg_len), _p(plan_status), _p(w), _p(result))
+        raise_for_status(st, self.ctx.handle)
+        return plan_status, (seg_first, seg_stream[:max_segs], seg_off[:max_segs], seg_len[:max_segs]), result
+
+    def frame_repair_streams(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", rep_framed: torch.Tensor,
+                             rep_off: torch.Tensor, rep_len: torch.Tensor, rep_index: "FrameIndex", chunk_bytes: int = N.BLOCK_SIZE):
+        """The damaged streams of a batch built again from their good chunks and replica t = s for the bad ones:
+        -> (damaged stream numbers, out, out_off, out_len, status, FrameIndex); output j is stream damaged[j].
+
+        frame_verify_indexed; ONE synchronising read of the streams that are not OK, their bad rows (a stream with b bad rows has at most
+        2 b + 1 segments, so the plan needs no sizing call) and the streams' row count; frame_repair_plan; the replicas copied once behind the streams (one torch.cat:
+        the compose call takes one tensor) with the two indexes joined as frame_restore_to_memory joins them; frame_compose_to_memory; and a
+        SECOND VERIFY, of the outputs: the replica chunks the compose copied were never checked.  status (int32) is the compose's where
+        that failed, else the second verify's, so damage on both sides in the same range shows as a stream that is still bad.  A stream
+        that was the identifier plus contiguous non-empty data chunks comes back byte for byte from an undamaged copy."""
+        dev = self.device
+        ns = in_len.numel()
+        row_status, status, nbad, *_ = self.frame_verify_indexed(framed, in_off, in_len, index)
+        seen = torch.cat([status.to(torch.int64), nbad, index.first[ns:ns + 1]]).tolist()
+        damaged = [s for s in range(ns) if seen[s] != N.OK]
+        if not damaged:
+            none = torch.zeros(0, dtype=torch.int64, device=dev)
+            empty = FrameIndex(torch.zeros(1, dtype=torch.int64, device=dev), none, none, none, torch.zeros(0, dtype=torch.int32, device=dev))
+            return damaged, torch.empty(0, dtype=torch.uint8, device=dev), none, none, torch.zeros(0, dtype=torch.int32, device=dev), empty
+        pairs = torch.tensor(damaged, dtype=torch.int32, device=dev)
+        max_segs = sum(2 * seen[ns + s] + 1 for s in damaged)
+        plan_status, recipe, _ = self.frame_repair_plan(index, row_status, rep_index, pairs, pairs, max_segs)
+        rows = min(seen[2 * ns], index.nentries)
+        sources = FrameIndex(torch.cat([index.first[:ns], rep_index.first + rows]), torch.cat([index.start[:rows], rep_index.start]),
+                             torch.cat([index.pos[:rows], rep_index.pos]), torch.cat([index.total, rep_index.total]),
+                             torch.cat([index.tail, rep_index.tail]))
+        out, out_off, out_len, cst, new_index = self.frame_compose_to_memory(
+            torch.cat([framed, rep_framed]), torch.cat([in_off.to(torch.int64), rep_off.to(torch.int64) + framed.numel()]),
+            torch.cat([in_len.to(torch.int64), rep_len.to(torch.int64)]), sources, *recipe, chunk_bytes=chunk_bytes)
+        again = self.frame_verify_indexed(out, out_off, out_len, new_index)[1]
+        final = torch.where(plan_status != N.OK, plan_status, torch.where(cst != N.OK, cst, again))
+        return damaged, out, out_off, out_len, final, new_index
+
     def frame_digest_indexed(self, framed: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, index: "FrameIndex", req_stream: torch.Tensor,
                              req_off: torch.Tensor, req_len: torch.Tensor, edge_cap: int | None = None, work: torch.Tensor | None = None):
         """The CRC-32C of any number of windows of what framed streams decode to, from the CRCs their chunk headers carry, with no decode of

@@ -7,7 +7,8 @@
                                             # libsnappier_hip_frame_compose.so, libsnappier_hip_frame_digest.so,
                                             # libsnappier_hip_frame_diff.so, libsnappier_hip_frame_find.so,
                                             # libsnappier_hip_frame_edit.so, libsnappier_hip_frame_cuts.so,
-                                            # libsnappier_hip_frame_dedup.so, libsnappier_hip_frame_recut.so
+                                            # libsnappier_hip_frame_dedup.so, libsnappier_hip_frame_recut.so,
+                                            # libsnappier_hip_frame_verify.so
                                             # (+ libsnappier_datagen.so, bench/test helper)
 """
 from __future__ import annotations
@@ -63,6 +64,8 @@ LIBS = {
     "libsnappier_hip_frame_dedup.so": ["frame_dedup.hip"],
     # include/snappier_hip_frame_recut.h: device batch recut of seekable framed streams to a caller's cut list -- the chunks that already are pieces copied, the others decoded and compressed again, with the new index -- the same kind of extension
     "libsnappier_hip_frame_recut.so": ["frame_recut.hip"],
+    # include/snappier_hip_frame_verify.h: device batch verify of seekable framed streams chunk by chunk in bounded scratch -- a verdict per index row, nothing written but verdicts -- and the planner that turns the verdicts into compose recipes over a replica -- the same kind of extension
+    "libsnappier_hip_frame_verify.so": ["frame_verify.hip"],
     "libsnappier_datagen.so": ["datagen.hip"],
 }
 # every library but the product and the data generator is an extension, linked against the product (LIBS keeps its order: the product is built first)

@@ -5,7 +5,7 @@
 // libsnappier_hip_frame_dedup.so (C-ABI: include/snappier_hip_frame_dedup.h), linked against libsnappier_hip.so.  DESIGN.md 4.27.
 //
 //   init      every row: no key, no flag, canon = none; every slot of the table: empty
-//   before    one workgroup: the largest clamped idx_first in front of every stream (a running maximum)
+//   before    one workgroup: the largest clamped idx_first in front of every stream (a running maximum; frame_before_device.h)
 //   verdict   a workgroup per stream: dd_stream, its rows walked by the threads (cc_add, the compose call's row check), joined; a stream that
 //             passed: per row its stream, its chunk's bytes and, unless empty, its key
 //   insert    one thread per row: the key's slot claimed by a 64-bit compare-and-swap, the slot's row lowered by an atomic minimum -- the lowest
@@ -24,6 +24,7 @@
 #include "capi_internal.h"
 #include "scan_tiles.h"
 #include "frame_dedup_device.h"
+#include "frame_before_device.h"
 #include "../../include/snappier_hip_frame_dedup.h"
 
 namespace {
@@ -32,7 +33,6 @@ static_assert(kDdNone == SNP_DEDUP_NONE, "SNP_DEDUP_NONE");
 
 // row flags
 constexpr u32 kNew = 1u, kLive = 2u, kUniq = 4u, kMerged = 8u, kColl = 16u, kBegin = 32u;
-constexpr u32 kBeforeItems = 4;
 
 struct DdArgs {
     const u8* in;
@@ -95,43 +95,6 @@ __global__ __launch_bounds__(256) void k_dd_init(u64 ne, u64 slots, DdWork w, u6
             w.trow[i] = kDdNoRow;
         }
         if (i < 4) w.tot[i] = 0;
-    }
-}
-
-// One workgroup: before[b] = the largest clamped idx_first[j], j < b.
-__global__ __launch_bounds__(256) void k_dd_before(DdArgs a, DdWork w)
-{
-    __shared__ u64 s_wave[4];
-    const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    u64 carry = 0;
-    for (u64 base = 0; base < a.ns; base += 256u * kBeforeItems) {
-        const u64 i0 = base + static_cast<u64>(tid) * kBeforeItems;
-        u64 v[kBeforeItems], m = 0;
-        for (u32 k = 0; k < kBeforeItems; ++k) {
-            v[k] = i0 + k < a.ns ? dd_first(a.x, i0 + k) : 0;
-            m = v[k] > m ? v[k] : m;
-        }
-        u64 incl = m;                                                   // running maximum over the wavefront, this thread's items included
-        for (u32 d = 1; d < 64; d <<= 1) {
-            const u64 y = __shfl_up(incl, d, 64);
-            if (lane >= d) incl = y > incl ? y : incl;
-        }
-        u64 excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 0;
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        u64 run = carry, all = carry;
-        for (u32 q = 0; q < 4; ++q) {
-            if (q < wave) run = s_wave[q] > run ? s_wave[q] : run;
-            all = s_wave[q] > all ? s_wave[q] : all;
-        }
-        __syncthreads();
-        run = excl > run ? excl : run;
-        for (u32 k = 0; k < kBeforeItems; ++k) {
-            if (i0 + k < a.ns) w.before[i0 + k] = run;
-            run = v[k] > run ? v[k] : run;
-        }
-        carry = all;
     }
 }
 
@@ -387,7 +350,7 @@ snp_status snp_frame_dedup_indexed_batch(snp_ctx* c, const uint8_t* in, const ui
     const u32 wide = static_cast<u32>(std::min<u64>((std::max(ne, slots) + 255) / 256, 1u << 16)), waves = static_cast<u32>((ne + 3) / 4);
     // every stream's verdict and the rows of those that passed; the leader of every key; canon
     hipLaunchKernelGGL(k_dd_init, dim3(wide), dim3(256), 0, s, ne, slots, w, canon);
-    hipLaunchKernelGGL(k_dd_before, dim3(1), dim3(256), 0, s, a, w);
+    hipLaunchKernelGGL(k_fr_before, dim3(1), dim3(256), 0, s, a.x, a.ns, w.before);
     hipLaunchKernelGGL(k_dd_verdict, dim3(ns), dim3(256), 0, s, a, w);
     if (ne) {
         hipLaunchKernelGGL(k_dd_insert, dim3(groups(ne)), dim3(256), 0, s, ne, slots, w);
